@@ -14,12 +14,19 @@ By default the steps are the product loop's: train_joint.Trainer.fit over W + K 
 host -> device copies, replay of the trainer's captured micro-step hipGraph, all-reduce, clip + AdamW);
 --via-trainer 0 replays one pre-staged batch instead (within 2 % of each other on one MI355X).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line; `roofline` and `cpu_baseline` are null.
+With --full it then also measures (each leg can still be turned off with its --no-* option):
   roofline     -- dominant kernel (by time) of an event-instrumented step run right after the timed
                   region, same process / stream / data: algorithmic FLOPs per launch / mean launch
-                  duration vs the dense bf16 MFMA peak (2.5 PFLOP/s).
+                  duration vs the dense bf16 MFMA peak (2.5 PFLOP/s); for joint at N=1 also the
+                  llm_only / flow_only steps (`branches`).
   cpu_baseline -- the CPU oracle (torch fp32, all host cores; oracle/ref_math.py = port of the
                   reference's math) on a bounded sample of the same workload, rank 0, N=1 only.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed, as DIR/<name>.npy
+(the last step's loss terms as float64 scalars; the LoRA weights and AdamW first moment after it as float32,
+a fixed seeded sample of DUMP_MAX_ELEMS entries when larger).  Weights, batches and dropout masks are seeded,
+so the same arguments give the same inputs on every run.
 """
 import argparse
 import contextlib
@@ -46,6 +53,26 @@ PEAK_HBM_GBPS = 8000.0      # HBM3E (same table)
 # algorithmic work per utterance, forward + backward, 2 x MAC (torch flop counter on the oracle, LoRA r = 16)
 GFLOP_PER_UTT = {500: {"joint": 468.9, "flow_only": 154.08, "llm_only": 314.83},
                  1000: {"joint": 1015.0, "flow_only": 386.08, "llm_only": 628.94}}
+
+DUMP_MAX_ELEMS = 1 << 22    # per dumped vector (16 MiB of float32): two vectors + scalars stay under 64 MB
+
+
+def dump_outputs(out_dir, losses, opt):
+    """--dump-outputs: the last timed step's loss terms, and the LoRA weights (fp32 masters) and AdamW first moment it left.
+    A vector longer than DUMP_MAX_ELEMS is cut to the same fixed, seeded, sorted index sample (it depends on its length only)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(float(v), dtype=np.float64) for k, v in losses.items()}
+    n = opt.n
+    idx = None
+    if n > DUMP_MAX_ELEMS:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+    for name, t in (("lora_params", opt.flat_p), ("adam_exp_avg", opt.m)):
+        t = t.detach().float().cpu()
+        arrays[name] = (t if idx is None else t[idx]).numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log(f"[bench] wrote {', '.join(sorted(arrays))} to {out_dir}" + (f" ({DUMP_MAX_ELEMS} of {n} vector entries)" if idx is not None else ""))
 
 
 def step_record(workload, frames, utt_per_s_per_gpu, dtype):
@@ -282,10 +309,11 @@ def pmc_mfma_busy(kernel: str):
     return None, None
 
 
-def trainer_run(a, jm, workload, dev, dtype, rank, world, steps, warmup):
+def trainer_run(a, jm, workload, dev, dtype, rank, world, steps, warmup, last=None):
     """The product loop: train_joint.Trainer.fit over W + K fresh synthetic batches; the timed region is bracketed from the
     trainer's per-step hook (barrier + synchronize on both sides).  Returns (seconds of the K steps, MAX over ranks; loss;
-    graph statistics; the trainer)."""
+    graph statistics; the trainer).  `last` (a dict, optional): `last["losses"]` holds the loss terms of the latest micro-step,
+    so after fit() those of the last timed step."""
     from cosyvoice_lora_finetune_framework_amd import dp
     from cosyvoice_lora_finetune_framework_amd.modules import Numerics
     from cosyvoice_lora_finetune_framework_amd.train_joint import JointLightningModule, SyntheticLoader, Trainer
@@ -312,6 +340,13 @@ def trainer_run(a, jm, workload, dev, dtype, rank, world, steps, warmup):
 
     tr = Trainer(max_epochs=1, accumulate_grad_batches=1, gradient_clip_val=1.0, save_checkpoints=False,
                  log_every_n_steps=0, train_mode=bool(a.dropout), use_graph=bool(a.graph), on_step_end=hook)
+    if last is not None:
+        micro_step = tr._micro_step
+
+        def keep(*args, **kw):
+            last["losses"] = micro_step(*args, **kw)
+            return last["losses"]
+        tr._micro_step = keep
     log(f"[bench] rank {rank}: Trainer.fit [{workload}] ({'hipGraph micro-step' if a.graph else 'eager'}); warm-up {warmup}, timing {steps} steps")
     with contextlib.redirect_stdout(sys.stderr):
         tr.fit(module, loader)
@@ -352,7 +387,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-branches", action="store_true", help="skip the llm_only / flow_only legs of roofline.branches (joint, N = 1)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the roofline leg (instrumented step, single-branch "
+                                                        "steps) and the CPU-oracle baseline; a plain run prints null for both")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.no_roofline = a.no_cpu_baseline = True
 
     from cosyvoice_lora_finetune_framework_amd import dp
     from cosyvoice_lora_finetune_framework_amd.hipops import functional as HF
@@ -385,7 +427,8 @@ def main():
         if a.warmup < 1:
             log("[bench] --via-trainer captures the batch layout in its first step: raising --warmup to 1")
             a.warmup = 1
-        elapsed, final_loss, trainer_stats, tr = trainer_run(a, jm, a.workload, dev, dtype, rank, world, a.steps, a.warmup)
+        last = {} if a.dump_outputs else None
+        elapsed, final_loss, trainer_stats, tr = trainer_run(a, jm, a.workload, dev, dtype, rank, world, a.steps, a.warmup, last)
         opt = tr.optimizer
         graph = True if (a.graph and trainer_stats["replays"] > 0) else None
     elif a.graph:
@@ -435,8 +478,11 @@ def main():
             torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(el)
         final_loss = float(loss)
+        last = {"losses": {"loss": loss}}
 
     log(f"[bench] timed region done: {elapsed / a.steps * 1e3:.2f} ms/step; device memory reserved {torch.cuda.memory_reserved() / 2**30:.1f} GiB")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last["losses"], opt)
     if os.environ.get("CVFT_BENCH_HOSTLAUNCH") and not a.via_trainer and graph is not None:
         hs, tot = [], []
         for _ in range(5):

@@ -33,7 +33,7 @@ rm -rf $OUT/counters
 cp $OUT/counters.json profiles/r4_counters.json; cp $OUT/counters.txt profiles/r4_counters.txt
 cp $OUT/pmc_traffic.json profiles/r4_pmc_traffic.json; cp $OUT/pmc_traffic_128x128.json profiles/r4_pmc_traffic_128x128.json
 for k in p256 96x256 block_tail_fwd block_link_fwd block_link_bwd block_qkv_fwd block_tail_wide_bwd; do [ -f $OUT/pmc_traffic_$k.json ] && cp $OUT/pmc_traffic_$k.json profiles/r4_pmc_traffic_$k.json; done
-CVFT_BENCH_DUMP_PROFILE=$OUT/insitu_gemm_table.txt python bench.py --steps 20 --warmup 5 > $OUT/bench_n1.log 2>&1
+CVFT_BENCH_DUMP_PROFILE=$OUT/insitu_gemm_table.txt python bench.py --full --steps 20 --warmup 5 > $OUT/bench_n1.log 2>&1
 tail -1 $OUT/bench_n1.log > $OUT/bench_n1.json
 python bench.py --workload flow_only --batch 8 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline 2>&1 | tail -1 > $OUT/bench_flow_only_b8.json
 python bench.py --workload flow_only --steps 20 --warmup 5 --no-cpu-baseline --no-roofline 2>&1 | tail -1 > $OUT/bench_flow_only_b16.json
