@@ -4,8 +4,9 @@
 cosyvoice/llm/llm.py:32-95 that ``JointLLMFlowModel._forward_llm`` consumes
 (llm_flow_model.py:118-179): text_embedding, text_encoder, text_encoder_affine_layer,
 llm_embedding, llm, llm_decoder, speech_embedding, spk_embed_affine_layer, sos_eos, task_id,
-speech_token_size.  Only the training forward (no-prompt) is built; AR sampling / Qwen2LM are
-out of scope.
+speech_token_size.  Built: the training forward (no-prompt) and the autoregressive generation of
+llm.py:147-228 (``sampling_ids`` / ``inference``, plus the batched ``inference_batch``) on the decode kernels of
+decode.py / csrc/decode.hip.  Qwen2LM / bistream inference are out of scope.
 
 MI355X-first: the ragged ``[sos, spk, text, task, speech]`` concat + ``-1`` padding
 (llm.py:88-95) is ONE row-gather kernel driven by an index map computed on the host from the
@@ -13,15 +14,21 @@ CPU-side length vectors (no device sync); the LM target never leaves int32 index
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Optional
+import collections
+import functools
+from typing import Any, Dict, Generator, List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
+from . import decode as DEC
+from . import utils as U
 from .config import LLM_MODEL_CONFIG
 from .hipops import functional as HF
 from .modules import Numerics, RelPosEncoder, _cached, hip_linear, to_len
 from .utils import IGNORE_ID
+
+MAX_TRIALS_MSG = ('sampling reaches max_trials {} and still get eos when ignore_eos is True, check your input!')
 
 
 class TransformerLM(nn.Module):
@@ -117,6 +124,192 @@ class TransformerLM(nn.Module):
         idx, tgt, lm_len, L = self.build_index_maps(batch['text_token_len'].cpu(), batch['speech_token_len'].cpu(),
                                                     batch['speech_token'].cpu(), B, Lx, Lt, self.speech_token_size, lm_pad, lm_min)
         return {'_lm_maps': (idx.to(device), tgt.to(device), lm_len.to(device), L)}
+
+
+    # ------------------------------------------------------------------ autoregressive generation (llm.py:147-228)
+    def sampling_ids(self, weighted_scores: torch.Tensor, decoded_tokens: List, sampling: int, ignore_eos: bool = True):
+        """Host form of llm.py:147-163: re-draw while the draw is EOS and ignore_eos, at most 100 re-draws."""
+        fn = self.sampling if self.sampling is not None else U.ras_sampling
+        trials = 0
+        while True:
+            top_ids = fn(weighted_scores, decoded_tokens, sampling)
+            if (not ignore_eos) or (self.speech_token_size not in top_ids):
+                return top_ids
+            trials += 1
+            if trials > 100:
+                raise RuntimeError(MAX_TRIALS_MSG.format(100))
+
+    def sampler_cfg(self) -> Optional[DEC.SamplerCfg]:
+        """The device sampler's parameters for ``self.sampling``, or None when it must be called on the host: None ->
+        ras_sampling defaults; a functools.partial of utils.ras_sampling / nucleus_sampling / random_sampling (keyword
+        parameters, top_k <= 64, win_size <= 64) -> that sampler on the device; anything else -> the host."""
+        s = self.sampling
+        if s is None:
+            return DEC.SamplerCfg("ras")
+        if not isinstance(s, functools.partial) or s.args:
+            return None
+        kw = dict(s.keywords)
+        if s.func is U.ras_sampling and set(kw) <= {"top_p", "top_k", "win_size", "tau_r"}:
+            cfg = DEC.SamplerCfg("ras", **kw)
+        elif s.func is U.nucleus_sampling and set(kw) <= {"top_p", "top_k"}:
+            cfg = DEC.SamplerCfg("nucleus", **kw)
+        elif s.func is U.random_sampling and not kw:
+            cfg = DEC.SamplerCfg("random")
+        else:
+            return None
+        if cfg.mode != "random" and not (1 <= cfg.top_k <= 64 and cfg.top_p > 0 and 0 <= cfg.win <= DEC.HIST):
+            return None
+        return cfg
+
+    def lm_input_rows(self, text, text_len, prompt_text, prompt_text_len, prompt_speech_token, prompt_speech_token_len,
+                      embedding):
+        """llm.py:181-210 for one request -> (lm_input rows [T0, llm_input_size] fp32, text length without the prompt)."""
+        dev = self.llm_decoder.weight.device
+        num, dt = self.numerics, self.numerics.dtype
+        text = torch.cat([prompt_text.reshape(1, -1).to(dev), text.reshape(1, -1).to(dev)], dim=1)
+        Lx = text.shape[1]
+        n_text = int(text_len) if not torch.is_tensor(text_len) else int(text_len.reshape(-1)[0])
+        n_prompt = int(prompt_text_len) if not torch.is_tensor(prompt_text_len) else int(prompt_text_len.reshape(-1)[0])
+        with torch.no_grad():
+            temb = HF.embed_gather(text, self._table(self.text_embedding, dt))
+            enc = self.text_encoder.forward_cl(temb, 1, Lx, to_len(torch.tensor([Lx]), dev), num, causal=True)
+            enc = hip_linear(self.text_encoder_affine_layer, enc).float()
+            parts = [self.llm_embedding.weight[self.sos_eos].detach().float().reshape(1, -1)]
+            if embedding is not None and embedding.shape[0] != 0:
+                parts.append(hip_linear(self.spk_embed_affine_layer, HF.l2norm_rows(embedding.to(dev), dt)).float())
+            parts += [enc, self.llm_embedding.weight[self.task_id].detach().float().reshape(1, -1)]
+            n_ps = int(prompt_speech_token_len) if not torch.is_tensor(prompt_speech_token_len) else \
+                int(prompt_speech_token_len.reshape(-1)[0])
+            if n_ps != 0:
+                parts.append(self.speech_embedding.weight.detach().float()[prompt_speech_token.reshape(-1)[:n_ps].to(dev)])
+        return torch.cat(parts, dim=0).contiguous(), n_text
+
+    MAX_SESSIONS = 4
+
+    def decode_session(self, B: int, cap: int) -> "DEC.LMDecodeSession":
+        """The weights are packed once per weight dtype (rebuilt when a parameter changes) and shared by the sessions;
+        sessions (K/V caches, positional tables, captured step) are kept per (batch, capacity bucket, dtype), the
+        MAX_SESSIONS most recently used ones."""
+        cap = DEC.bucket(cap)
+        ver = tuple(p._version for p in self.parameters())
+        dtype = self.numerics.dtype
+        packs = self.__dict__.setdefault("_cvft_decode_weights", {})
+        sessions = self.__dict__.setdefault("_cvft_sessions", collections.OrderedDict())
+        pk = packs.get(dtype)
+        if pk is None or pk[0] != ver:
+            for k in [k for k in sessions if k[2] == dtype]:
+                del sessions[k]
+            packs[dtype] = pk = (ver, DEC.PackedLM(self))
+        key = (B, cap, dtype)
+        hit = sessions.get(key)
+        if hit is None:
+            hit = sessions[key] = (ver, DEC.LMDecodeSession(pk[1], B, cap))
+            while len(sessions) > self.MAX_SESSIONS:
+                sessions.popitem(last=False)
+        sessions.move_to_end(key)
+        return hit[1]
+
+    def _request_seed(self) -> int:
+        # one draw of torch's default generator per request (torch.manual_seed makes a run reproducible)
+        return int(torch.randint(0, 2 ** 62, (1,), device=self.llm_decoder.weight.device).item())
+
+    @torch.no_grad()
+    def inference(self, text: torch.Tensor, text_len: torch.Tensor, prompt_text: torch.Tensor,
+                  prompt_text_len: torch.Tensor, prompt_speech_token: torch.Tensor, prompt_speech_token_len: torch.Tensor,
+                  embedding: torch.Tensor, sampling: int = 25, max_token_text_ratio: float = 20,
+                  min_token_text_ratio: float = 2, uuid: str = '', use_graph: bool = True, seed: Optional[int] = None,
+                  uniforms: Optional[torch.Tensor] = None) -> Generator[int, None, None]:
+        """llm.py:165-228: yields speech-token ids until EOS (not yielded) or max_len.  `text_len` counts the text
+        WITHOUT the prompt (the reference adds prompt_text_len).  Extra keywords: use_graph=False runs the same
+        kernels without capture; seed / uniforms pin the sampler's draws (default: one seed per request drawn from
+        torch's generator)."""
+        rows, n_text = self.lm_input_rows(text, text_len, prompt_text, prompt_text_len, prompt_speech_token,
+                                          prompt_speech_token_len, embedding)
+        min_len, max_len = int(n_text * min_token_text_ratio), int(n_text * max_token_text_ratio)
+        if max_len <= 0:
+            return
+        cfg = self.sampler_cfg()
+        sess = self.decode_session(1, rows.shape[0] + max_len)
+        if cfg is None:
+            yield from self._inference_host(sess, rows, min_len, max_len, sampling, use_graph)
+            return
+        sess.start([rows], [min_len], [max_len], [self._request_seed() if seed is None else seed], cfg,
+                   uniforms=uniforms)
+        while True:
+            tok, done, err = sess.read()
+            if err[0]:
+                raise RuntimeError(MAX_TRIALS_MSG.format(100))
+            if tok[0] == self.speech_token_size:
+                return
+            yield tok[0]
+            if done[0]:
+                return
+            sess.advance(use_graph)
+
+    def _inference_host(self, sess, rows, min_len, max_len, sampling, use_graph):
+        """an arbitrary ``self.sampling`` callable: device logits / log_softmax, the draw on the host per step."""
+        sess.start([rows], [0], [max_len], [0], DEC.SamplerCfg("logp"))
+        out: List[int] = []
+        for i in range(max_len):
+            logp = sess.logp[0].clone()
+            if i == 0:
+                logp[self.speech_token_size] = -float('inf')
+            top = int(self.sampling_ids(logp, out, sampling, ignore_eos=i < min_len))
+            if top == self.speech_token_size:
+                return
+            yield top
+            out.append(top)
+            if i + 1 == max_len:
+                return
+            sess.next_in.fill_(top)
+            sess.advance(use_graph)
+            sess.stack.len.add_(1)
+
+    @torch.no_grad()
+    def inference_batch(self, texts: Sequence[torch.Tensor], embeddings: Optional[Sequence[torch.Tensor]] = None,
+                        prompt_texts: Optional[Sequence[torch.Tensor]] = None,
+                        prompt_speech_tokens: Optional[Sequence[torch.Tensor]] = None,
+                        seeds: Optional[Sequence[int]] = None, max_token_text_ratio: float = 20,
+                        min_token_text_ratio: float = 2, use_graph: bool = True) -> List[List[int]]:
+        """Up to 16 requests (ragged) decoded in lockstep: each is prefilled into its own cache row, then every step
+        streams the weights once for all rows; finished rows are skipped by the kernels.  Returns one token list per
+        request, equal to what ``inference`` yields for that request with the same seed."""
+        B = len(texts)
+        assert 1 <= B <= 16, "inference_batch: 1 .. 16 requests"
+        cfg = self.sampler_cfg()
+        if cfg is None:
+            raise NotImplementedError("inference_batch runs the device sampler only (see sampler_cfg)")
+        z = torch.zeros(0, dtype=torch.long)
+        rows, mins, maxs = [], [], []
+        for b in range(B):
+            pt = prompt_texts[b] if prompt_texts is not None else z
+            ps = prompt_speech_tokens[b] if prompt_speech_tokens is not None else z
+            emb = embeddings[b] if embeddings is not None else torch.zeros(1, 192)
+            r, n = self.lm_input_rows(texts[b].reshape(-1), texts[b].numel(), pt.reshape(-1), pt.numel(),
+                                      ps.reshape(-1), ps.numel(), emb.reshape(1, -1) if emb.numel() else emb)
+            rows.append(r)
+            mins.append(int(n * min_token_text_ratio))
+            maxs.append(max(int(n * max_token_text_ratio), 0))
+        seeds = [self._request_seed() for _ in range(B)] if seeds is None else list(seeds)
+        outs: List[List[int]] = [[] for _ in range(B)]
+        if max(maxs) <= 0:
+            return outs
+        sess = self.decode_session(B, max(r.shape[0] + m for r, m in zip(rows, maxs)))
+        sess.start(rows, mins, [max(m, 1) for m in maxs], seeds, cfg)
+        active = [m > 0 for m in maxs]
+        while any(active):
+            tok, done, err = sess.read()
+            for b in range(B):
+                if not active[b]:
+                    continue
+                if err[b]:
+                    raise RuntimeError(MAX_TRIALS_MSG.format(100))
+                if tok[b] != self.speech_token_size:
+                    outs[b].append(tok[b])
+                active[b] = not done[b]
+            if any(active):
+                sess.advance(use_graph)
+        return outs
 
 
 def build_llm_model(pretrained_path: Optional[str] = None, device: str = 'cuda', numerics: Optional[Numerics] = None,

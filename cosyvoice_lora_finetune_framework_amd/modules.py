@@ -705,6 +705,13 @@ class RelPosEncoder(nn.Module):
             x = layer(x, pos_emb, B, L, length, causal, num.enc_ln_eps)
         return hip_layernorm(self.after_norm, x)
 
+    def forward_chunk(self, xs, offset: int, required_cache_size: int, att_cache=torch.zeros(0, 0, 0, 0),
+                      cnn_cache=torch.zeros(0, 0, 0, 0), att_mask=torch.ones((0, 0, 0), dtype=torch.bool)):
+        """encoder.py:184-273 (batch 1, causal, cache (elayers, head, t, d_k*2)) on the decode kernels (decode.py);
+        cnn_cache is unused (TransformerEncoder) and returned empty."""
+        from .decode import forward_chunk
+        return forward_chunk(self, xs, offset, required_cache_size, att_cache, cnn_cache, att_mask)
+
     def forward(self, xs, xs_lens, decoding_chunk_size: int = 0, num_decoding_left_chunks: int = -1,
                 num: Optional[Numerics] = None):
         """Reference signature: xs (B,L,D), xs_lens (B,) -> (B,L,d), masks (B,1,L) bool."""

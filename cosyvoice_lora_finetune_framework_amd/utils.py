@@ -60,3 +60,38 @@ def pad_list(xs, pad_value: int):
     for i, x in enumerate(xs):
         out[i, :len(x)] = x
     return out
+
+
+# ---------------------------------------------------------------------------------------------- token samplers
+# Host forms of the reference samplers (cosyvoice/utils/common.py:111-139), same signatures.  The decode session
+# (decode.py) runs a functools.partial of these on the device with the partial's parameters; any other callable is
+# called here on the host once per step.
+def nucleus_sampling(weighted_scores: torch.Tensor, top_p: float = 0.8, top_k: int = 25) -> torch.Tensor:
+    """Draw from the candidates of the stable descending order, taken while their cumulative probability is below
+    top_p and fewer than top_k are taken (so the candidate that crosses top_p is included); the draw is proportional to
+    the candidates' un-renormalised probabilities."""
+    probs, order = weighted_scores.softmax(dim=0).sort(descending=True, stable=True)
+    cum = torch.zeros((), dtype=probs.dtype, device=probs.device)
+    n = 0
+    while n < len(order) and bool(cum < top_p) and n < top_k:
+        cum = cum + probs[n]
+        n += 1
+    pick = probs[:n].multinomial(1, replacement=True)
+    return order[:n][pick]
+
+
+def random_sampling(weighted_scores: torch.Tensor, decoded_tokens, sampling) -> torch.Tensor:
+    """One draw from the full softmax."""
+    return weighted_scores.softmax(dim=0).multinomial(1, replacement=True)
+
+
+def ras_sampling(weighted_scores: torch.Tensor, decoded_tokens, sampling, top_p: float = 0.8, top_k: int = 25,
+                 win_size: int = 10, tau_r: float = 0.1) -> torch.Tensor:
+    """Repetition-aware sampling (VALL-E 2): a nucleus draw, replaced by a draw from the full softmax when the drawn id
+    already occurs at least win_size * tau_r times among the last win_size decoded tokens."""
+    top_ids = nucleus_sampling(weighted_scores, top_p=top_p, top_k=top_k)
+    recent = list(decoded_tokens)[-win_size:] if win_size > 0 else []
+    rep = sum(1 for t in recent if int(t) == int(top_ids))
+    if rep >= win_size * tau_r:
+        top_ids = random_sampling(weighted_scores, decoded_tokens, sampling)
+    return top_ids

@@ -509,6 +509,41 @@ int cvft_debug_stamp(unsigned long long* buf, int slot, void* stream);
  * OCP e4m3 bytes with unit block scales -- pins the operand layout the fp8 GEMM will use (tests/test_ops_gpu.py). */
 int cvft_debug_mfma_fp8_probe(const void* A, const void* B, float* C, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Autoregressive decode (TransformerLM.inference, llm.py:165-228; decode.hip).  Activations, K/V caches and the
+ * positional tables are fp32; weights fp32 or bf16 (`wdtype`), stored [N][K] like nn.Linear, LoRA already folded.
+ *
+ * cvft_decode_linear: Y[m,n] = act(LN?(X)[m,:] . W[n,:] + bias[n]) (+ residual[m,n]) for M <= 16 rows.  ln_g / ln_b
+ *   non-NULL: LayerNorm(eps) of each X row first (every workgroup redoes the row statistics).  act: 0 none, 1 relu.
+ *   residual may alias Y.  K % 8 == 0.
+ * cvft_decode_attn: rel-pos attention of Lq <= 16 new rows per sequence against that sequence's K/V cache
+ *   (attention.py:225-330 with the full cache: score = ((q+u).k_j + (q+v).P[i-j]) * scale, causal).  qkv
+ *   [B*Lq][ldqkv] holds q | k | v of the new rows (H*64 each); kc / vc [B][H][cap][64]; len[b] (device) = cached rows
+ *   before this call; the new rows' K/V are appended at len[b] .. len[b]+Lq-1 (caller guarantees len+Lq <= cap).
+ *   P [>= cap][ldp]: P[d] = linear_pos(pe at relative distance d >= 0).  done[b] != 0 (or done NULL = none): row skipped,
+ *   nothing written to its cache, o rows zero.  Keys are split over `nsplit` workgroups of 256 keys (nsplit*256 >= cap);
+ *   part = workspace of B*H*nsplit*Lq*66 floats, combined by a second launch.
+ * cvft_decode_sample: one workgroup per row b (not done): logp = log_softmax(logits[b]) (written to logp if non-NULL);
+ *   step 0 -> logp[eos] = -inf; probabilities = softmax(logp); mode 0 RAS (common.py:111-139: nucleus over the stable
+ *   descending order while cum < top_p and count < top_k, top_k <= 64; the drawn id redrawn from the full softmax when it
+ *   occurs >= rep_thr times among the last `win` history tokens), 1 nucleus only, 2 full softmax.  Before min_len[b] a
+ *   drawn EOS is re-drawn (trials 0..100; then err[b] = 1 and done[b] = 1).  Draws use uniforms[(b*101+trial)*2+draw]
+ *   if non-NULL, else a counter-based generator keyed by (seeds[b], step, trial, draw).  Then tok[b] = id; EOS: done;
+ *   else next_in[b] = id, history ring hist[b][hist_cap] / nhist[b] appended, len[b] += 1, step[b] += 1, done when
+ *   step reaches max_len[b].  mode 3: logp only (no draw, no state change).  V <= 8192.
+ * ------------------------------------------------------------------------------- */
+int cvft_decode_linear(int wdtype, int M, int N, int K, const float* X, int ldx, const float* ln_g, const float* ln_b,
+                       float ln_eps, const void* W, const float* bias, int act, const float* residual, int ldr, float* Y,
+                       int ldy, void* stream);
+int cvft_decode_attn(int B, int H, int Lq, int cap, int nsplit, const float* qkv, int ldqkv, float* kc, float* vc,
+                     const int32_t* len, const int32_t* done, const float* P, int ldp, const float* pos_bias_u,
+                     const float* pos_bias_v, float scale, float* part, float* o, int ldo, void* stream);
+int cvft_decode_sample(int B, int V, const float* logits, int ldl, float* logp, int eos, int mode, int top_k,
+                       float top_p, int win, int rep_thr, const uint64_t* seeds, const float* uniforms, int32_t* tok,
+                       int32_t* next_in, int32_t* hist, int hist_cap, int32_t* nhist, int32_t* step,
+                       const int32_t* min_len, const int32_t* max_len, int32_t* len, int32_t* done, int32_t* err,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
