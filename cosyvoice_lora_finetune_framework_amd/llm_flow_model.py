@@ -38,26 +38,16 @@ BRANCH_STREAMS = os.environ.get("CVFT_BRANCH_STREAMS", "1") != "0"      # LLM br
 
 
 LOSS_FUSE = os.environ.get("CVFT_LOSS_FUSE", "1") != "0"      # 0: the plain op-per-factor recombination (A/B)
-# 1: the trainer issues every chain's backward right behind its forward (forward_backward: no join of all chains between the two
-# directions); 0 (default): forward(), then ONE backward of the total, the reference's order.  Measured neutral, same box, 40 steps:
-# joint 21.28 / 21.36 (1) vs 21.33 / 21.34 ms (0), flow_only 14.29 vs 14.27, llm_only 13.38 vs 13.31 -- the step is bound by the
-# chip's CU-time, an idle chain is another chain's CUs
-# Every chain's backward issued right behind its own forward on the chain's stream (forward_backward), and the chain's postponed
-# adapter products flushed there too: "0" = the reference's order (forward of all chains, one weighted total, one backward).  Neutral
-# while the optimiser ran outside the captured step (21.28 / 21.36 vs 21.33 / 21.34); with it inside, the step's single-stream tail
-# behind the join is what the chains' own flush shortens: 20.13 / 20.20 / 20.19 -> 20.02 / 20.05 / 20.10 ms (three same-box pairs).
-# "auto" (default): on in the joint mode; the single-branch modes lose 0.03 ms with it (flow_only 14.25 -> 14.28, llm_only 12.82 -> 12.86).
-CHAIN_BWD = os.environ.get("CVFT_CHAIN_BWD", "auto")
 
 
-def chain_bwd_on(model) -> bool:
-    if CHAIN_BWD in ("0", "1"):
-        return CHAIN_BWD == "1"
-    return getattr(model, "training_mode", None) == 'joint'
-CHAIN_FLUSH = os.environ.get("CVFT_CHAIN_FLUSH", "1") != "0"      # (with CHAIN_BWD: LoraGradSink.flush_chain behind each chain's backward)
-# Diagnostic: with CVFT_CHAIN_EVENTS=1 (and CVFT_CHAIN_BWD=1) forward_backward drops a clock stamp (cvft_debug_stamp: a one-thread
-# kernel node, HIP refuses timing events inside a captured graph) at the fork, behind every chain's forward and backward, and at the
-# join; bench.py prints their offsets after the run: which chain ends the step, and how long the others have been done by then.
+def loss_terms(training_mode: str) -> tuple:
+    """the loss terms a training mode trains, in the order of the trainer's per-term weight vector"""
+    return {'joint': ('llm', 'flow'), 'llm_only': ('llm',), 'flow_only': ('flow',)}[training_mode]
+
+
+# Diagnostic: with CVFT_CHAIN_EVENTS=1 the chain loop drops a clock stamp (cvft_debug_stamp: a one-thread kernel node, HIP refuses
+# timing events inside a captured graph) at the fork, behind every chain's forward (and backward), and at the join; bench.py prints
+# their offsets after the run: which chain ends the step, and how long the others have been done by then.
 CHAIN_EVENTS = {} if os.environ.get("CVFT_CHAIN_EVENTS", "0") != "0" else None
 _CHAIN_STAMPS = []
 
@@ -79,8 +69,6 @@ def chain_event_offsets_ms():
     t = _CHAIN_STAMPS[0].cpu().tolist()
     t0 = t[CHAIN_EVENTS[('fork',)]]
     return {k: (t[s] - t0) / 1e5 for k, s in CHAIN_EVENTS.items()}
-CHAIN_ORDER = int(os.environ.get("CVFT_CHAIN_ORDER", "0"))      # 1: chains enqueued Flow first, LLM last (the caller's stream then carries the LLM) -- see forward()
-SIDE_STREAM_PRIORITY = int(os.environ.get("CVFT_SIDE_PRIO", "0"))      # priority of the side streams (the Flow chains in joint mode): -1 = high
 
 
 def _scaled(x, w):
@@ -128,111 +116,70 @@ class JointLLMFlowModel(nn.Module):
         the stream its forward ran on, so the overlap holds for the whole step, and inside a captured hipGraph it costs
         one fork and one join per chain and direction.  Sub-batch losses are recombined with their share of the global
         denominators (frames for the CFM loss, target tokens for the CE loss): the reference's global-batch means."""
-        losses: Dict[str, Any] = {}
+        return self._run_chains(self._step_parts(batch, device), device, draws)
+
+    def forward_backward(self, batch: dict, device, draws: Optional[dict] = None, term_w=None, accum: int = 1) -> Dict[str, Any]:
+        """forward() + the backward of  sum_k term_w[k] * losses[k + '_loss'] / accum  (k over loss_terms(training_mode); term_w:
+        the trainer's data-parallel loss weights, a device vector, None = ones), CHAIN BY CHAIN: every chain's backward is issued
+        on the chain's own stream right behind its forward, followed by the chain's postponed adapter products.  The chains share
+        nothing but leaf parameters and the loss denominators (host-known shares, `_w_llm` / `_w_flow`), so a chain's seed
+        gradient -- term_w[k] x branch weight x its share / accum -- is known before its forward has run; nothing makes the LLM
+        chain's backward wait for the Flow chains' forward (forward() + loss.backward() joins all chains on one stream between the
+        two directions: the earlier chain idles there and the chip runs under-filled until the last forward chain has finished).
+        Call inside a LoraGradSink (the adapters' slab products of all chains meet in its one reduce).  Returns forward()'s
+        dict, detached.  Same masks, same arithmetic per chain; the loss scalars are recombined exactly as in forward()."""
+        parts = self._step_parts(batch, device)
+        # seed gradients, made on the caller's stream BEFORE the chains fork (every chain waits for that stream first)
+        branch_w = {'llm': float(self.llm_loss_weight), 'flow': float(self.flow_loss_weight)}
+        seeds = {}
+        for i, kind in enumerate(loss_terms(self.training_mode)):
+            c = branch_w[kind] / float(accum)
+            tw = None if term_w is None else term_w[i]
+            for k, part in enumerate(parts[kind]):
+                share = part['_w_' + kind]
+                if torch.is_tensor(share):
+                    sd = share.to(torch.float32) * c
+                    sd = sd if tw is None else sd * tw
+                elif tw is not None:
+                    sd = tw.to(torch.float32) * (c * float(share))
+                else:
+                    sd = torch.full((), c * float(share), dtype=torch.float32, device=device)
+                seeds[(kind, k)] = sd
+
+        def backward(kind, k, loss):
+            torch.autograd.backward([loss], [seeds[(kind, k)].to(loss.dtype)])
+            if HF.LoraGradSink.active is not None:
+                HF.LoraGradSink.active.flush_chain()      # this chain's postponed adapter products, on its own stream
+        return self._run_chains(parts, device, draws, backward)
+
+    def _step_parts(self, batch: dict, device) -> dict:
+        """start of a step: new dropout masks (training), and the sub-batches the chains run on (`_make_parts`)"""
         if self.training:
             HF.dropout_begin_step()       # new dropout masks per step (device-side seed: also across hipGraph replays)
         parts = batch.get('_parts')
-        if parts is None:
-            parts = self._make_parts(batch, batch, device, torch.cuda.is_available())
-        do_llm = self.training_mode in ('joint', 'llm_only')
-        do_flow = self.training_mode in ('joint', 'flow_only')
-        chains = [('llm', k) for k in range(len(parts['llm']))] * do_llm + [('flow', k) for k in range(len(parts['flow']))] * do_flow
-        if CHAIN_ORDER and len(chains) == 3:      # (A/B: which chain keeps the caller's stream and in which order the others fork)
-            import itertools
-            chains = [chains[i] for i in list(itertools.permutations(range(3)))[CHAIN_ORDER % 6]]
+        return parts if parts is not None else self._make_parts(batch, batch, device, torch.cuda.is_available())
+
+    def _run_chains(self, parts: dict, device, draws: Optional[dict], backward=None) -> Dict[str, Any]:
+        """One chain per branch this mode trains and sub-batch (`parts`), each forked onto a stream of its own (the last stays on
+        the caller's), joined, and their losses recombined into forward()'s dict.  backward(kind, k, loss), if given, runs on
+        the chain's stream right behind its forward; the dict then holds detached values."""
+        terms = loss_terms(self.training_mode)
+        chains = [(kind, k) for kind in terms for k in range(len(parts[kind]))]
         use_streams = BRANCH_STREAMS and torch.cuda.is_available() and len(chains) > 1
         if torch.cuda.is_available():      # tile-shape hint for the kernels that would own a whole CU (cvft.h)
             HF.lib().cvft_set_concurrent_chains(CHAINS_HINT if CHAINS_HINT else (len(chains) if use_streams else 1))
         HF.LoraGradSink.uses_hint = max(len(v) for v in parts.values())      # chains that will run the same adapters
         cur = torch.cuda.current_stream() if use_streams else None
-        results = {}
-        for ci, (kind, k) in enumerate(reversed(chains)):          # the last chain (flow part 0 ... ) stays on the caller's stream
-            st = None
-            if use_streams and ci < len(chains) - 1:
-                while len(JointLLMFlowModel._streams) <= ci:
-                    JointLLMFlowModel._streams.append(torch.cuda.Stream(priority=SIDE_STREAM_PRIORITY))
-                st = JointLLMFlowModel._streams[ci]
-                st.wait_stream(cur)
-            with (torch.cuda.stream(st) if st is not None else contextlib.nullcontext()):
-                part = parts[kind][k]
-                # (every scalar op here is a launch of its own on the joined stream, with the whole chip waiting between the
-                # last forward chain and the first backward launch -- and another one or two in backward: unit factors are skipped)
-                if kind == 'llm':
-                    r = self._forward_llm(part, device)
-                    results[(kind, k)] = (_scaled(r['loss'], part['_w_llm']), _scaled(r['acc'], part['_w_llm']) if 'acc' in r else None)
-                else:
-                    d = None if draws is None else {n_: v[part['_rows']] if '_rows' in part else v for n_, v in draws.items()}
-                    r = self._forward_flow(part, device, d)
-                    results[(kind, k)] = (_scaled(r['loss'], part['_w_flow']), None)
-            if st is not None:
-                results[(kind, k)] = (results[(kind, k)], st)
-        for key, v in list(results.items()):                       # join
-            if isinstance(v[0], tuple):
-                cur.wait_stream(v[1])
-                results[key] = v[0]
-        if do_llm:
-            losses['llm_loss'] = _scaled(_total([results[('llm', k)][0] for k in range(len(parts['llm']))]), self.llm_loss_weight)
-            if results[('llm', 0)][1] is not None:
-                losses['llm_acc'] = _total([results[('llm', k)][1] for k in range(len(parts['llm']))])
-        if do_flow:
-            losses['flow_loss'] = _scaled(_total([results[('flow', k)][0] for k in range(len(parts['flow']))]), self.flow_loss_weight)
-        if self.training_mode == 'joint':
-            losses['loss'] = losses['llm_loss'] + losses['flow_loss']
-        elif self.training_mode == 'llm_only':
-            losses['loss'] = losses['llm_loss']
-        else:
-            losses['loss'] = losses['flow_loss']
-        return losses
-
-    def forward_backward(self, batch: dict, device, draws: Optional[dict] = None, term_w=None, accum: int = 1) -> Dict[str, Any]:
-        """forward() + the backward of  sum_k term_w[k] * losses[k + '_loss'] / accum  (k over the branches this mode runs, in the
-        order 'llm', 'flow'; term_w: the trainer's data-parallel loss weights, a device vector, None = ones), CHAIN BY CHAIN:
-        every chain's backward is issued on the chain's own stream right behind its forward.  The chains share nothing but leaf
-        parameters and the loss denominators (host-known shares, `_w_llm` / `_w_flow`), so a chain's seed gradient --
-        term_w[k] x branch weight x its share / accum -- is known before its forward has run; nothing makes the LLM chain's
-        backward wait for the Flow chains' forward (forward() + loss.backward() joins all chains on one stream between the two
-        directions: the earlier chain idles there and the chip runs under-filled until the last forward chain has finished).
-        Call inside a LoraGradSink (the adapters' slab products of all chains meet in its one reduce).  Returns forward()'s
-        dict, detached.  Same masks, same arithmetic per chain; the loss scalars are recombined exactly as in forward()."""
-        losses: Dict[str, Any] = {}
-        if self.training:
-            HF.dropout_begin_step()
-        parts = batch.get('_parts')
-        if parts is None:
-            parts = self._make_parts(batch, batch, device, torch.cuda.is_available())
-        do_llm = self.training_mode in ('joint', 'llm_only')
-        do_flow = self.training_mode in ('joint', 'flow_only')
-        chains = [('llm', k) for k in range(len(parts['llm']))] * do_llm + [('flow', k) for k in range(len(parts['flow']))] * do_flow
-        use_streams = BRANCH_STREAMS and torch.cuda.is_available() and len(chains) > 1
-        if torch.cuda.is_available():
-            HF.lib().cvft_set_concurrent_chains(CHAINS_HINT if CHAINS_HINT else (len(chains) if use_streams else 1))
-        HF.LoraGradSink.uses_hint = max(len(v) for v in parts.values())
-        cur = torch.cuda.current_stream() if use_streams else None
-        # seed gradients, made on the caller's stream BEFORE the chains fork (every chain waits for that stream first)
-        terms = [k for k in ('llm', 'flow') if (k == 'llm' and do_llm) or (k == 'flow' and do_flow)]
-        branch_w = {'llm': float(self.llm_loss_weight), 'flow': float(self.flow_loss_weight)}
-        seeds = {}
-        for kind, k in chains:
-            share = parts[kind][k]['_w_llm' if kind == 'llm' else '_w_flow']
-            c = branch_w[kind] / float(accum)
-            tw = None if term_w is None else term_w[terms.index(kind)]
-            if torch.is_tensor(share):
-                sd = share.to(torch.float32) * c
-                sd = sd if tw is None else sd * tw
-            elif tw is not None:
-                sd = tw.to(torch.float32) * (c * float(share))
-            else:
-                sd = torch.full((), c * float(share), dtype=torch.float32, device=device)
-            seeds[(kind, k)] = sd
-        results = {}
+        results, forked = {}, []
         _chain_event(('fork',))
-        for ci, (kind, k) in enumerate(reversed(chains)):
+        for ci, (kind, k) in enumerate(reversed(chains)):          # the last chain (flow part 0 ... ) stays on the caller's stream
             st = None
             if use_streams and ci < len(chains) - 1:
                 while len(JointLLMFlowModel._streams) <= ci:
                     JointLLMFlowModel._streams.append(torch.cuda.Stream())
                 st = JointLLMFlowModel._streams[ci]
                 st.wait_stream(cur)
+                forked.append(st)
             with (torch.cuda.stream(st) if st is not None else contextlib.nullcontext()):
                 part = parts[kind][k]
                 if kind == 'llm':
@@ -240,33 +187,26 @@ class JointLLMFlowModel(nn.Module):
                 else:
                     d = None if draws is None else {n_: v[part['_rows']] if '_rows' in part else v for n_, v in draws.items()}
                     r = self._forward_flow(part, device, d)
-                loss = r['loss']
+                loss, acc = r['loss'], r.get('acc')
                 _chain_event((kind, k, 'forward done'))
-                torch.autograd.backward([loss], [seeds[(kind, k)].to(loss.dtype)])
-                if CHAIN_FLUSH and HF.LoraGradSink.active is not None:
-                    HF.LoraGradSink.active.flush_chain()      # this chain's postponed adapter products, on its own stream
-                _chain_event((kind, k, 'backward done'))
-                share = part['_w_llm' if kind == 'llm' else '_w_flow']
-                results[(kind, k)] = (_scaled(loss.detach(), share), _scaled(r['acc'].detach(), share) if 'acc' in r else None)
-            if st is not None:
-                results[(kind, k)] = (results[(kind, k)], st)
-        for key, v in list(results.items()):                       # join
-            if isinstance(v[0], tuple):
-                cur.wait_stream(v[1])
-                results[key] = v[0]
+                if backward is not None:
+                    backward(kind, k, loss)
+                    _chain_event((kind, k, 'backward done'))
+                    loss, acc = loss.detach(), None if acc is None else acc.detach()
+                # (every scalar op here is a launch of its own on the joined stream, with the whole chip waiting between the
+                # last forward chain and the first backward launch -- and another one or two in backward: unit factors are skipped)
+                share = part['_w_' + kind]
+                results[(kind, k)] = (_scaled(loss, share), None if acc is None else _scaled(acc, share))
+        for st in forked:                                          # join
+            cur.wait_stream(st)
         _chain_event(('join',))
-        if do_llm:
-            losses['llm_loss'] = _scaled(_total([results[('llm', k)][0] for k in range(len(parts['llm']))]), self.llm_loss_weight)
-            if results[('llm', 0)][1] is not None:
-                losses['llm_acc'] = _total([results[('llm', k)][1] for k in range(len(parts['llm']))])
-        if do_flow:
-            losses['flow_loss'] = _scaled(_total([results[('flow', k)][0] for k in range(len(parts['flow']))]), self.flow_loss_weight)
-        if self.training_mode == 'joint':
-            losses['loss'] = losses['llm_loss'] + losses['flow_loss']
-        elif self.training_mode == 'llm_only':
-            losses['loss'] = losses['llm_loss']
-        else:
-            losses['loss'] = losses['flow_loss']
+        losses: Dict[str, Any] = {}
+        for kind in terms:
+            n = len(parts[kind])
+            losses[f'{kind}_loss'] = _scaled(_total([results[(kind, k)][0] for k in range(n)]), getattr(self, f'{kind}_loss_weight'))
+            if results[(kind, 0)][1] is not None:
+                losses[f'{kind}_acc'] = _total([results[(kind, k)][1] for k in range(n)])
+        losses['loss'] = losses['llm_loss'] + losses['flow_loss'] if len(terms) == 2 else losses[f'{terms[0]}_loss']
         return losses
 
     def _prepare_one(self, batch: dict, device, lm_pad: int = 1, with_llm: bool = True, lm_min: int = 0) -> dict:
@@ -274,7 +214,7 @@ class JointLLMFlowModel(nn.Module):
         for k in ('speech_token_len', 'speech_feat_len', 'text_token_len'):
             if k in out:
                 out[k] = out[k].to(torch.int32)
-        if with_llm and self.training_mode in ('joint', 'llm_only') and hasattr(self.llm, 'prepare_batch') and 'text_token' in batch:
+        if with_llm and 'llm' in loss_terms(self.training_mode) and hasattr(self.llm, 'prepare_batch') and 'text_token' in batch:
             out.update(self.llm.prepare_batch(batch, device, lm_pad, lm_min))
         return out
 
@@ -314,7 +254,7 @@ class JointLLMFlowModel(nn.Module):
         B = batch['speech_token'].shape[0]
         parts = {}
         for kind in ('llm', 'flow'):
-            runs = self.training_mode in ('joint', f'{kind}_only')          # a branch the mode does not run is never split
+            runs = kind in loss_terms(self.training_mode)          # a branch the mode does not run is never split
             n = SPLIT_LLM_ONLY if (kind == 'llm' and self.training_mode == 'llm_only') else SPLIT[kind]
             min_part = SPLIT_MIN_PART_FLOW_ONLY if self.training_mode == 'flow_only' else SPLIT_MIN_PART
             if not (split and runs) or B < n * min_part:
@@ -339,21 +279,22 @@ def build_joint_model(pretrained_path: str = PRETRAINED_MODEL_DIR, device: str =
     print(f"[Joint] building CosyVoice-300M LLM + Flow (weights from {pretrained_path})")
     llm = build_llm_model(pretrained_path, device='cpu', numerics=numerics)
     flow = build_flow_model(pretrained_path, device='cpu', numerics=numerics)
-    if training_mode in ('joint', 'llm_only') and llm_lora_config:
+    terms = loss_terms(training_mode)
+    if 'llm' in terms and llm_lora_config:
         st = apply_lora_to_model(llm, r=llm_lora_config.get('lora_r', 8), lora_alpha=llm_lora_config.get('lora_alpha', 16),
                                  lora_dropout=llm_lora_config.get('lora_dropout', 0.05),
                                  target_modules=llm_lora_config.get('target_modules', ['linear_q', 'linear_k', 'linear_v', 'linear_out', 'w_1', 'w_2']))
         print(f"  LLM LoRA: {st['replaced_layers']} layers, {st['trainable_params']:,} params ({st['trainable_ratio']:.2f}%)")
-    if training_mode in ('joint', 'flow_only') and flow_lora_config:
+    if 'flow' in terms and flow_lora_config:
         st = apply_lora_to_model(flow, r=flow_lora_config.get('lora_r', 16), lora_alpha=flow_lora_config.get('lora_alpha', 16),
                                  lora_dropout=flow_lora_config.get('lora_dropout', 0.05),
                                  target_modules=flow_lora_config.get('target_modules', ['to_q', 'to_k', 'to_v', 'linear_q', 'linear_k', 'linear_v', 'linear_out', 'w_1', 'w_2']))
         print(f"  Flow LoRA: {st['replaced_layers']} layers, {st['trainable_params']:,} params ({st['trainable_ratio']:.2f}%)")
     # freeze the branch the mode never trains (the reference leaves it
     # "trainable" but gradient-less; behaviourally identical, no 300M-param optimiser state).
-    if training_mode == 'flow_only':
+    if 'llm' not in terms:
         llm.requires_grad_(False)
-    if training_mode == 'llm_only':
+    if 'flow' not in terms:
         flow.requires_grad_(False)
     jc = JOINT_TRAINING_CONFIG
     model = JointLLMFlowModel(llm, flow, training_mode, jc.get('llm_loss_weight', 1.0), jc.get('flow_loss_weight', 1.0),

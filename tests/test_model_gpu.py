@@ -557,6 +557,73 @@ def test_sub_batch_chains_with_gradient_sink(tiny_meta, dtype):
         assert worst[0] < tol, worst
 
 
+@pytest.mark.parametrize("mode", ["joint", "llm_only", "flow_only"])
+def test_forward_backward_equals_forward_then_weighted_backward(tiny_meta, mode):
+    """The trainer's chain-by-chain step (JointLLMFlowModel.forward_backward: every chain's backward behind its own forward)
+    against the reference's order (forward of all chains, train_joint._weighted_total, one backward), with per-term weights
+    that are not ones, gradient accumulation, dropout on and several sub-batch chains on several streams: same loss dict,
+    same LoRA gradients."""
+    import copy
+    from cosyvoice_lora_finetune_framework_amd import llm_flow_model as J
+    from cosyvoice_lora_finetune_framework_amd import train_joint as TJ
+    from cosyvoice_lora_finetune_framework_amd.hipops import functional as HF
+    from cosyvoice_lora_finetune_framework_amd.lora import LoRALinear
+    from cosyvoice_lora_finetune_framework_amd.modules import Numerics
+    from cosyvoice_lora_finetune_framework_amd.synthetic import cfm_draws, synth_batch
+    meta = copy.deepcopy(tiny_meta)
+    for k in ("flow", "llm"):
+        meta[k]["lora"]["r"], meta[k]["lora"]["alpha"] = 16, 32
+    num = Numerics(dtype=torch.float32)
+    flow = build_flow_product(meta["flow"], DEV, num)
+    llm = build_llm_product(meta["llm"], DEV, num)
+    for m in list(flow.modules()) + list(llm.modules()):
+        if isinstance(m, LoRALinear):
+            m.lora_dropout = torch.nn.Dropout(0.1)
+    jm = J.JointLLMFlowModel(llm, flow, mode, 2.0, 1.5).to(DEV).train()
+    batch = synth_batch([24, 17, 21, 19], text_lens=[7, 5, 6, 4], token_lens=[13, 9, 11, 10], seed=11, text_vocab=100, speech_vocab=50)
+    draws = cfm_draws(4, 24, seed=5)
+    terms = J.loss_terms(mode)
+    term_w = torch.tensor([0.7, 1.3][:len(terms)], device=DEV)
+    accum = 2
+    params = [(n, p) for n, p in jm.named_parameters() if p.requires_grad]
+
+    def chain_by_chain():
+        with HF.LoraGradSink():
+            return jm.forward_backward(batch, DEV, draws, term_w, accum)
+
+    def reference_order():
+        out = jm(batch, DEV, draws)
+        total = TJ._weighted_total(out, terms, term_w, accum)
+        with HF.LoraGradSink():
+            total.backward()
+        return out
+
+    saved = (dict(J.SPLIT), J.SPLIT_LLM_ONLY, J.SPLIT_MIN_PART, J.SPLIT_MIN_PART_FLOW_ONLY)
+    J.SPLIT.update({'llm': 2, 'flow': 2})
+    J.SPLIT_LLM_ONLY, J.SPLIT_MIN_PART, J.SPLIT_MIN_PART_FLOW_ONLY = 2, 1, 1
+    outs = []
+    try:
+        for run in (reference_order, chain_by_chain):
+            for _, p in params:
+                p.grad = torch.zeros_like(p, dtype=torch.float32)
+            HF.set_dropout_seed_state(4321)
+            torch.manual_seed(0)
+            out = run()
+            torch.cuda.synchronize()
+            outs.append(({k: float(v) for k, v in out.items()}, {n: p.grad.clone() for n, p in params}))
+    finally:
+        J.SPLIT.clear()
+        J.SPLIT.update(saved[0])
+        J.SPLIT_LLM_ONLY, J.SPLIT_MIN_PART, J.SPLIT_MIN_PART_FLOW_ONLY = saved[1:]
+    (ref_losses, ref_grads), (losses, grads) = outs
+    assert set(losses) == set(ref_losses)
+    for k in ref_losses:
+        assert math.isclose(losses[k], ref_losses[k], rel_tol=1e-5), (k, losses[k], ref_losses[k])
+    assert any(float(g.norm()) > 0 for g in ref_grads.values())
+    worst = max((rel(grads[k], ref_grads[k]), k) for k in ref_grads)
+    assert worst[0] < 1e-4, worst
+
+
 def test_shape_bucketed_batch_equals_exact_batch(tiny_meta):
     """train_joint.Trainer._fit_layout: a batch padded up to the layout of another captured step (T, Lt, text, LM length all
     larger, `_true_dims` = the exact maxima) gives the exact batch's losses and LoRA gradients -- the length regulator's
