@@ -82,3 +82,10 @@ def keep_fields_host(seed: int, site: int, ngroups: int):
 def drop_thr_host(p: float) -> int:
     import numpy as np
     return int(min(65535.0, float(np.rint(np.float32(p) * np.float32(65536.0)))))
+
+
+def keep_scale_host(seed: int, site: int, n: int, p: float):
+    """Host replica of common.h cvft_drop_key / cvft_keep4 (keep_fields_host): flat [n] fp64 tensor of {0, 1/(1-p)}."""
+    import numpy as np
+    u = keep_fields_host(seed, site, (n + 3) // 4).reshape(-1)[:n].astype(np.uint64)
+    return torch.from_numpy((u >= np.uint64(drop_thr_host(p))).astype(np.float64)) / (1.0 - float(np.float32(p)))

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import keep_scale_host as _keep_scale_host
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -1173,14 +1175,6 @@ def test_attn_relpos_probability_dropout(dtype, causal):
     orf.backward(gy.double())
     assert rel(o.reshape(B, L, -1), orf) < TOL[dtype]
     assert rel(qd.grad.reshape(B, L, -1), qr.grad) < TOL[dtype] * 3
-
-
-def _keep_scale_host(seed: int, site: int, n: int, p: float) -> torch.Tensor:
-    """Host replica of common.h cvft_drop_key / cvft_keep4 (tests/helpers.py: keep_fields_host): flat [n] tensor of {0, 1/(1-p)}."""
-    import numpy as np
-    from helpers import drop_thr_host, keep_fields_host
-    u = keep_fields_host(seed, site, (n + 3) // 4).reshape(-1)[:n].astype(np.uint64)
-    return torch.from_numpy((u >= np.uint64(drop_thr_host(p))).astype(np.float64)) / (1.0 - float(np.float32(p)))
 
 
 @pytest.mark.parametrize("r", [16, 64])
