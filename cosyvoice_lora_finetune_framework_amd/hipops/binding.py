@@ -94,6 +94,16 @@ class GemmArgs(C.Structure):
     ]
 
 
+class HiftConvArgs(C.Structure):
+    """mirror of cvft_hift_conv_args (include/cvft.h)"""
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("Tin", C.c_int), ("Tq", C.c_int), ("Tout", C.c_int),
+                ("out_stride", C.c_int), ("out_off", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("CoutP", C.c_int),
+                ("ntaps", C.c_int), ("tap_off", C.c_int * 11), ("x", C.c_void_p), ("ldx", C.c_int), ("W", C.c_void_p),
+                ("bias", C.c_void_p), ("pre", C.c_int), ("alpha", C.c_void_p), ("slope", C.c_float), ("elu", C.c_int),
+                ("res", C.c_void_p), ("ldr", C.c_int), ("res2", C.c_void_p), ("ldr2", C.c_int),
+                ("accum", C.c_int), ("scale", C.c_float), ("y", C.c_void_p), ("ldy", C.c_int)]
+
+
 _i, _f, _p, _i64 = C.c_int, C.c_float, C.c_void_p, C.c_int64
 
 # name -> argtypes (restype is int unless noted).  Must list every symbol of include/cvft.h.
@@ -163,6 +173,12 @@ SIGNATURES = {
     "cvft_decode_attn": [_i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _f, _p, _p, _i, _p],
     "cvft_decode_sample": [_i, _i, _p, _i, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
                            _p],
+    "cvft_hift_conv": [C.POINTER(HiftConvArgs), _p],
+    "cvft_hift_conv_small": [_i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _i, _p],
+    "cvft_hift_scan": [_i, _i, _i, _p, _f, _p, _p],
+    "cvft_hift_source": [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p],
+    "cvft_hift_stft": [_i, _i, _p, _p, _p],
+    "cvft_hift_istft": [_i, _i, _p, _i, _f, _p, _p, _p],
 }
 
 _lib: Optional[C.CDLL] = None

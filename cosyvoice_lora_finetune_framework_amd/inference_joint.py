@@ -1,15 +1,20 @@
-"""Text token ids -> speech tokens (the fine-tuned LLM) -> mel (the fine-tuned Flow): the no-prompt path of the
-reference's inference_joint.py (empty prompt, zero speaker embedding), without the text front-end and the vocoder.
+"""Text token ids -> speech tokens (the fine-tuned LLM) -> mel (the fine-tuned Flow) -> waveform (the HiFT vocoder,
+with ``--hift``): the no-prompt path of the reference's inference_joint.py (empty prompt, zero speaker embedding),
+without the text front-end.
 
     python -m cosyvoice_lora_finetune_framework_amd.inference_joint --llm merged/llm.pt --flow merged/flow.pt \\
         --text-tokens 12,873,44,9 --out mel.npy [--speed 0.9] [--seed 0] [--dtype bf16]
         [--top-p 0.8 --top-k 25 --win-size 10 --tau-r 0.1] [--llm-config '{...}' --flow-config '{...}'] [--noise z.npy]
+        [--hift hift.pt --wav out.wav [--hift-dtype fp32] [--hift-seed 0]]
 
 ``--llm`` / ``--flow`` are the merged state_dicts ``merge_joint_weights.py`` writes; ``--text-tokens`` is a comma-separated
 id list or a ``.npy`` file of ids.  The mel is de-normalised with MEL_MEAN / MEL_STD and written as [80, T] float32.
 The LLM samples with ``utils.ras_sampling`` and the given parameters (``--top-k 1 --tau-r 1e9`` is greedy).
 ``--llm-config`` / ``--flow-config`` are JSON keyword arguments of ``build_llm_model`` / ``build_flow_model`` for models
 of other dimensions than CosyVoice-300M; ``--noise`` pins the Flow's initial noise ([1, 80, T] ``.npy``).
+``--hift`` is the HiFT generator's state_dict (``hift.pt``); with it the mel also goes through ``hift.HiFTGenerator`` and
+``--wav`` is written as 16-bit PCM at 22 050 Hz.  ``--hift-dtype`` is the vocoder's weight dtype (fp32 by default),
+``--hift-seed`` pins its source's random phase and noise.  Without ``--hift`` only the mel is written.
 """
 from __future__ import annotations
 
@@ -17,6 +22,7 @@ import argparse
 import functools
 import json
 import os
+import wave
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -49,6 +55,26 @@ def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] =
     return tokens, mel
 
 
+@torch.no_grad()
+def vocode(hift, mel: torch.Tensor, seed: Optional[int] = None, draws=None, dtype=None) -> torch.Tensor:
+    """de-normalised mel (B, 80, T) -> waveform (B, T*256) fp32 in [-0.99, 0.99] at 22 050 Hz (hift.HiFTGenerator)."""
+    wav, _ = hift.inference(mel, draws=draws, seed=seed, dtype=dtype)
+    return wav
+
+
+def pcm16(wav: torch.Tensor) -> np.ndarray:
+    return np.clip(np.rint(wav.detach().float().cpu().numpy() * 32767.0), -32768, 32767).astype('<i2')
+
+
+def write_wav(path: str, wav: torch.Tensor, rate: int = 22050) -> None:
+    """mono 16-bit PCM of wav [T] (values in [-1, 1])."""
+    with wave.open(path, 'wb') as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(rate)
+        f.writeframes(pcm16(wav.reshape(-1)).tobytes())
+
+
 def _text_tokens(arg: str) -> List[int]:
     if os.path.exists(arg):
         return [int(v) for v in np.load(arg).reshape(-1)]
@@ -74,6 +100,10 @@ def main(argv=None):
     ap.add_argument('--llm-config', default='{}', help='JSON keyword arguments of build_llm_model')
     ap.add_argument('--flow-config', default='{}', help='JSON keyword arguments of build_flow_model')
     ap.add_argument('--noise', default=None, help='.npy of the Flow\'s initial noise [1, 80, T]')
+    ap.add_argument('--hift', default=None, help='HiFT generator state_dict (hift.pt): also vocode the mel')
+    ap.add_argument('--wav', default='out.wav', help='with --hift: the waveform, 16-bit PCM at 22 050 Hz')
+    ap.add_argument('--hift-dtype', choices=('fp32', 'bf16'), default='fp32')
+    ap.add_argument('--hift-seed', type=int, default=None)
     a = ap.parse_args(argv)
     num = Numerics(dtype=torch.bfloat16 if a.dtype == 'bf16' else torch.float32)
     kw = lambda js: {k: tuple(v) if isinstance(v, list) else v for k, v in json.loads(js).items()}   # noqa: E731
@@ -88,6 +118,13 @@ def main(argv=None):
     tokens, mel = synthesize(llm, flow, _text_tokens(a.text_tokens), a.speed, a.seed, noise=noise)
     np.save(a.out, mel[0].cpu().numpy().astype(np.float32))
     print(f"{len(tokens)} speech tokens -> mel {tuple(mel.shape[1:])} -> {a.out}")
+    if a.hift:
+        from .hift import HiFTGenerator
+        voc = HiFTGenerator(dtype=torch.bfloat16 if a.hift_dtype == 'bf16' else torch.float32)
+        voc.load_state_dict(torch.load(a.hift, map_location='cpu', weights_only=True), strict=True)
+        wav = vocode(voc.to(dev).eval(), mel, seed=a.hift_seed)
+        write_wav(a.wav, wav[0], voc.sampling_rate)
+        print(f"mel -> {wav.shape[1]} samples at {voc.sampling_rate} Hz -> {a.wav}")
 
 
 if __name__ == '__main__':

@@ -544,6 +544,62 @@ int cvft_decode_sample(int B, int V, const float* logits, int ldl, float* logp, 
                        const int32_t* min_len, const int32_t* max_len, int32_t* len, int32_t* done, int32_t* err,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * HiFT vocoder, inference only (hifigan/generator.py HiFTGenerator.inference, f0_predictor.py; hift.hip).
+ * Activations are channel-last fp32 rows [B*T][C]; weights fp32 or bf16 (`dtype`), weight norm already folded.
+ *
+ * cvft_hift_conv: a convolution as an implicit tap-GEMM on the matrix cores (generator.py:94-101 ResBlock.forward,
+ *   :524-546 conv_pre / ups / conv_post, f0_predictor.py:31-52 condnet).  Per batch row b and output position q < Tq:
+ *     y[b*Tout + q*out_stride + out_off][n] = epi(sum_j pre(x)[b*Tin + q + tap_off[j]][:] . W[j][n][:] + bias[n])
+ *   with x rows outside [0, Tin) read as zero.  A workgroup stages its 64 positions plus the halo (min .. max tap_off,
+ *   span <= 50) of one 64-channel slab into LDS once, applying `pre` while staging (0 none, 1 Snake
+ *   x + sin^2(alpha x) / (alpha + 1e-9) with per-channel alpha -- `alpha` must hold Cin floats, the padded count, which
+ *   the entry cannot check --, 2 leaky-ReLU with `slope`); every tap is a shifted read
+ *   of that image.  epi: v = acc + bias; elu != 0: ELU(v); += res[row] (ldr); += res2[row] (ldr2); accum != 0: += y's
+ *   old value; *= scale.  res / res2 rows are indexed like y and may alias y.  W: [ntaps][CoutP][Cin] in `dtype`
+ *   (operands are rounded to `dtype` when staged; accumulation fp32), CoutP = Cout rounded up to 64 (padded rows are
+ *   read, not stored); Cin % 64 == 0, ldx % 4 == 0, 1 <= ntaps <= 11.  A stride-s transposed convolution is s launches,
+ *   one per output phase (out_stride = s, out_off = phase).
+ * cvft_hift_conv_small: the narrow edges as a plain direct convolution, fp32 (generator.py:466-471 source_downs,
+ *   f0_predictor.py:53-58 classifier + abs): y[b*Tout + t][n] = epi(sum_{j,c} x[b*Tin + t*stride - pad + j][c] *
+ *   W[j][c][n] + bias[n]), zero outside [0, Tin); absval != 0: |v|.
+ * cvft_hift_scan: y[r][n] = fp32(sum_{m <= n} (double)(x[r][m / rep] / div)), n < L (generator.py:149-151: the
+ *   correctly rounded fp32 division by the sampling rate, then torch.cumsum, which accumulates fp32 input in fp64 on
+ *   the CPU); x [R][ceil(L / rep)]; div = 1 leaves x as it is.
+ * cvft_hift_source: SineGen + SourceModuleHnNSF (generator.py:147-171, :216-219) from the scanned phases:
+ *   s[b][n] = tanh(sum_h lw[h] * (0.1 sin(2 pi (cum[b][h][n] mod 1) + phase[b][h]) * uv + namp * noise[b][h][n]) + lb),
+ *   uv = f0[b][n / rep] > thr, namp = uv ? 0.003 : 0.1 / 3; uv_out [B][L] (optional).  H <= 16.
+ * cvft_hift_stft: n_fft 16, hop 4, periodic Hann, centre reflect padding (generator.py:504-510):
+ *   out[b*(L/4+1) + f][0..8] = real, [9..17] = imag; L % 4 == 0, L >= 16.
+ * cvft_hift_istft: generator.py:512-518, :547-551: mag = min(exp(x[:, :9]), 100), phase = sin(x[:, 9:]), inverse
+ *   16-point real DFT, Hann window, overlap-add over the 4 frames of a sample, / window envelope, centre trim, clamp to
+ *   +-limit.  x [B*F][ldx >= 18], wav [B][4*(F-1)]; mag_out [B*F][9] (optional) receives the clipped magnitudes.
+ * ------------------------------------------------------------------------------- */
+typedef struct {
+    int dtype;
+    int B, Tin, Tq, Tout, out_stride, out_off;
+    int Cin, Cout, CoutP;
+    int ntaps;
+    int tap_off[11];
+    const float* x; int ldx;
+    const void* W;
+    const float* bias;
+    int pre; const float* alpha; float slope;
+    int elu;
+    const float* res; int ldr;
+    const float* res2; int ldr2;
+    int accum; float scale;
+    float* y; int ldy;
+} cvft_hift_conv_args;
+int cvft_hift_conv(const cvft_hift_conv_args* a, void* stream);
+int cvft_hift_conv_small(int B, int Tin, int Tout, int Cin, int Cout, int k, int stride, int pad, const float* x, int ldx,
+                         const float* W, const float* bias, int absval, float* y, int ldy, void* stream);
+int cvft_hift_scan(int R, int L, int rep, const float* x, float div, float* y, void* stream);
+int cvft_hift_source(int B, int H, int L, int rep, const float* f0, const float* cum, const float* phase,
+                     const float* noise, const float* lw, const float* lb, float thr, float* s, float* uv_out, void* stream);
+int cvft_hift_stft(int B, int L, const float* s, float* out, void* stream);
+int cvft_hift_istft(int B, int F, const float* x, int ldx, float limit, float* wav, float* mag_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
