@@ -311,33 +311,63 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(GP<T> p) {
 template <typename T>
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+const GemmKnobs& gemm_knobs() {
+    static const GemmKnobs knobs = [] {
+        GemmKnobs k;
+        const auto rd = [](const char* name, auto& v) { if (const char* s = getenv(name)) v = atol(s); };
+        rd("CVFT_GLDS_CFG", k.glds_cfg); rd("CVFT_GLDS_DIRECT", k.glds_direct); rd("CVFT_GLDS_NS", k.glds_ns);
+        rd("CVFT_GLDS_BIG_T64", k.glds_big_t64); rd("CVFT_GLDS_BIG", k.glds_big); rd("CVFT_GLDS_WIDE", k.glds_wide);
+        rd("CVFT_GLDS_RECT", k.glds_rect); rd("CVFT_P256", k.p256); rd("CVFT_P256_SPLIT", k.p256_split);
+        rd("CVFT_P256_HB", k.p256_hb); rd("CVFT_P256_ROWSPLIT", k.p256_rowsplit); rd("CVFT_P256_STAMP", k.p256_stamp);
+        rd("CVFT_P256_SLAB_BF16", k.p256_slab_bf16); rd("CVFT_P256_NARROW", k.p256_narrow); rd("CVFT_P256_GRID", k.p256_grid);
+        rd("CVFT_SKINNY_MT", k.skinny_mt);
+        return k;
+    }();
+    return knobs;
+}
+
 template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU = false>
-static int gemm_launch_cfg(const GP<T>& p, hipStream_t st) {
-    constexpr int VEC = 16 / sizeof(T);
-    constexpr int BK = (sizeof(T) == 2) ? 64 : 16;
-    constexpr int LD = BK + VEC;
-    size_t ring = (size_t)2 * (BM + BN + (FU ? 16 : 0)) * LD * sizeof(T);
-    size_t cs = (size_t)BM * (BN + 4) * sizeof(float);
-    size_t sm = ring > cs ? ring : cs;
+static int gemm_launch_cfg(const GemmLaunch<T>& l, hipStream_t st, bool enqueue) {
     auto kern = gemm_kernel<T, BM, BN, WM, WN, D, AL, FU>;
-    static bool attr_set = false;             // per instantiation; a host call per launch is visible in eager mode
-    if (sm > 48 * 1024 && !attr_set) {
-        attr_set = true;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) {
-            cvft_set_error("cvft_gemm: hipFuncSetAttribute(%zu) failed: %s", sm, hipGetErrorString(e));
-            return -2;
-        }
-    }
-    long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(WM * WN * 64), sm, st, p);
-    cvft_set_kernel_label("gemm_kernel<%s,%d,%d,%d,%d>%s", sizeof(T) == 2 ? "bf16" : "f32", BM, BN, WM, WN, FU ? ",fusedU" : "");
-    CVFT_LAUNCH_CHECK("cvft_gemm");
+    static bool attr_set = false;
+    if (!enqueue) return gemm_lds_attr(reinterpret_cast<const void*>(kern), l.lds, attr_set);
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.block), l.lds, st, l.p);
     return 0;
 }
 
+// the register-staged kernel on tile configuration <BM, BN, WM, WN, D> as the plan's only launch
+template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU = false>
+static int gemm_plan_cfg(const GP<T>& p, GemmPlan<T>& plan) {
+    constexpr int VEC = 16 / sizeof(T);
+    constexpr int BK = (sizeof(T) == 2) ? 64 : 16;
+    constexpr int LD = BK + VEC;
+    const size_t ring = (size_t)2 * (BM + BN + (FU ? 16 : 0)) * LD * sizeof(T);
+    const size_t cs = (size_t)BM * (BN + 4) * sizeof(float);
+    GemmLaunch<T>& l = plan.l[0];
+    plan.n = 1;
+    l.fn = gemm_launch_cfg<T, BM, BN, WM, WN, D, AL, FU>;
+    l.p = p; l.lds = ring > cs ? ring : cs; l.block = WM * WN * 64;
+    l.grid = (unsigned)((long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN));
+    snprintf(l.label, sizeof(l.label), "gemm_kernel<%s,%d,%d,%d,%d>%s", sizeof(T) == 2 ? "bf16" : "f32", BM, BN, WM, WN, FU ? ",fusedU" : "");
+    return 0;
+}
+
+// bf16 launches with 16-byte rows: the skinny, 256x256 and LDS-DMA kernels take every shape they are eligible for, in that
+// order; 1 = none is (CVFT_GLDS_CFG=-1: all three off; experiments)
+static int gemm_plan_dma(const GP<bf16_t>& p, const GemmKnobs& k, int chains, GemmPlan<bf16_t>& plan) {
+    if (k.glds_cfg < 0) return 1;
+    plan.n = 1;
+    if (p.N <= 64 && p.xdrop_p <= 0.f && skinny_plan(p, k, plan.l[0]) == 0) return 0;
+    const int rc = gemm_p256_plan(p, k, chains, plan);
+    if (rc != 1) return rc;
+    plan.n = 1;
+    return gemm_glds_plan(p, k, chains, plan.l[0]);
+}
+
+// Fills GP from the (validated) arguments and chooses the launches.  Host arithmetic only: pointers are looked at for
+// NULL and alignment, never dereferenced, and no HIP API is called.
 template <typename T>
-static int gemm_launch(const cvft_gemm_args* a, hipStream_t st) {
+static int gemm_plan(const cvft_gemm_args* a, const GemmKnobs& k, int chains, GemmPlan<T>& plan) {
     constexpr int VEC = 16 / sizeof(T);
     GP<T> p;
     p.M = a->M; p.N = a->N; p.K = a->K; p.Tm = a->Tm; p.Tin = a->Tin; p.Tout = a->Tout;
@@ -355,7 +385,7 @@ static int gemm_launch(const cvft_gemm_args* a, hipStream_t st) {
     for (int i = 0; i < 4; ++i) p.xdrop_sites[i] = a->xdrop_sites[i];
     p.odrop_p = a->odrop_p; p.odrop_site = a->odrop_site; p.row_off = 0;
     if (p.odrop_p > 0.f) {
-        if (!p.xdrop_seed || !cvft_drop_rate_ok(p.odrop_p) || p.N % 4 != 0 || p.ldc != p.N || p.Tm != p.M || p.out_stride != 1 || p.out_off != 0 || p.Tout != p.Tm) {
+        if (!p.xdrop_seed || !cvft_drop_rate_ok(p.odrop_p) || p.N % 4 != 0 || p.ldc != p.N || !gemm_ident_out(p) || p.Tout != p.Tm) {
             cvft_set_error("cvft_gemm: output dropout needs a seed, 2^-16 <= p <= 1 - 2^-16, N %% 4 == 0, ldc == N and identity row geometry");
             return -1;
         }
@@ -376,7 +406,7 @@ static int gemm_launch(const cvft_gemm_args* a, hipStream_t st) {
     const size_t bU = p.R > 0 ? (size_t)p.M * p.ldu * sizeof(T) : 0, bB = p.R > 0 ? (size_t)p.N * p.ldbl * sizeof(T) : 0;
     const size_t lim = 0x7fff0000u;
     p.bytesA = (unsigned)bA; p.bytesW = (unsigned)bW; p.bytesU = (unsigned)bU; p.bytesB = (unsigned)bB;
-    long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
+    const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
     bool al = p.vecA && p.vecW && bA < lim && bW < lim;
     if (p.fuse) {
         const size_t bL = (size_t)p.R * p.ldla * sizeof(T);
@@ -389,57 +419,46 @@ static int gemm_launch(const cvft_gemm_args* a, hipStream_t st) {
             cvft_set_error("cvft_gemm: fused LoRA side path needs 16-byte aligned operands, K %% %d == 0 and N > 32", VEC);
             return -1;
         }
-        long t128f = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
         if constexpr (sizeof(T) == 2) {
-            static const int gcfg = getenv("CVFT_GLDS_CFG") ? atoi(getenv("CVFT_GLDS_CFG")) : 0;
-            if (gcfg >= 0) {
-                int rc = gemm_glds_launch(p, st, gcfg);
-                if (rc != 1) return rc;
-            }
+            const int rc = gemm_plan_dma(p, k, chains, plan);
+            if (rc != 1) return rc;
         }
-        if (p.R > 16) {
+        if (p.R > 16) {         // the register-staged kernel stages one rank tile; cvft_gemm admits R <= 48 for the LDS-DMA kernel's three
             cvft_set_error("cvft_gemm: fused LoRA side path with 16 < R <= 48 needs the bf16 LDS-DMA kernel (K %% 64 == 0, identity rows)");
             return -1;
         }
         if constexpr (sizeof(T) == 2) {
-            if (p.K >= 2048 && t128f >= 256) return gemm_launch_cfg<T, 256, 128, 4, 2, 2, true, true>(p, st);
+            if (p.K >= 2048 && t128 >= 256) return gemm_plan_cfg<T, 256, 128, 4, 2, 2, true, true>(p, plan);
         }
-        return gemm_launch_cfg<T, 64, 64, 2, 2, 4, true, true>(p, st);
+        return gemm_plan_cfg<T, 64, 64, 2, 2, 4, true, true>(p, plan);
     }
+    // register-staged kernels: any R whose U / Bl rows are whole 16-byte vectors (no rank tiles, so no R % 8 / R <= 64 as in gemm_rank_ext_ok)
     al = al && (p.R == 0 || (p.vecU && p.vecB)) && bU < lim && bB < lim;
     if (al) {
         if constexpr (sizeof(T) == 2) {
-            // LDS-DMA kernels take every eligible shape (CVFT_GLDS_CFG: -1 = off; experiments)
-            static const int gcfg = getenv("CVFT_GLDS_CFG") ? atoi(getenv("CVFT_GLDS_CFG")) : 0;
-            if (gcfg >= 0 && p.N <= 64 && p.xdrop_p <= 0.f) {
-                int rc = skinny_launch(p, st);
-                if (rc != 1) return rc;
-            }
-            if (gcfg >= 0) {
-                int rc = gemm_glds_launch(p, st, gcfg);
-                if (rc != 1) return rc;
-            }
+            const int rc = gemm_plan_dma(p, k, chains, plan);
+            if (rc != 1) return rc;
         }
         if (p.xdrop_p > 0.f) {
             cvft_set_error("cvft_gemm: masked rank extension: launch not eligible for the LDS-DMA register-epilogue kernels");
             return -1;
         }
-        if (p.N <= 32) return gemm_launch_cfg<T, 32, 32, 2, 1, 4, true>(p, st);
-        // measured on MI355X (tools/bench_kernels.py, CVFT_GEMM_CFG sweep): 64x64 tiles with 4 k-tiles in flight win
+        if (p.N <= 32) return gemm_plan_cfg<T, 32, 32, 2, 1, 4, true>(p, plan);
+        // measured on MI355X (tools/bench_kernels.py, tile sweep): 64x64 tiles with 4 k-tiles in flight win
         // on every step shape up to K = 1024; long-K GEMMs (w_2 dgrad / forward, K = 4096) prefer 256x128 x 8 waves.
         if constexpr (sizeof(T) == 2) {
-            if (p.ntaps * p.K >= 2048 && t128 >= 256) return gemm_launch_cfg<T, 256, 128, 4, 2, 2, true>(p, st);
+            if (p.ntaps * p.K >= 2048 && t128 >= 256) return gemm_plan_cfg<T, 256, 128, 4, 2, 2, true>(p, plan);
         }
-        return gemm_launch_cfg<T, 64, 64, 2, 2, 4, true>(p, st);
+        return gemm_plan_cfg<T, 64, 64, 2, 2, 4, true>(p, plan);
     }
     if (p.xdrop_p > 0.f) {
         cvft_set_error("cvft_gemm: masked rank extension needs 16-byte aligned operands");
         return -1;
     }
-    return gemm_launch_cfg<T, 64, 64, 2, 2, 2, false>(p, st);     // unaligned / odd-K operands: generic element loads
+    return gemm_plan_cfg<T, 64, 64, 2, 2, 2, false>(p, plan);     // unaligned / odd-K operands: generic element loads
 }
 
-extern "C" int cvft_gemm(const cvft_gemm_args* a, void* stream) {
+static int gemm_check_args(const cvft_gemm_args* a) {
     CVFT_CHECK_ARG(a != nullptr, "cvft_gemm: null args");
     CVFT_CHECK_ARG(a->dtype == CVFT_F32 || a->dtype == CVFT_BF16, "cvft_gemm: bad dtype %d", a->dtype);
     CVFT_CHECK_ARG(a->M >= 0 && a->N > 0 && a->K > 0, "cvft_gemm: bad M/N/K %d %d %d", a->M, a->N, a->K);
@@ -463,8 +482,46 @@ extern "C" int cvft_gemm(const cvft_gemm_args* a, void* stream) {
     CVFT_CHECK_ARG(!a->dact_src || a->ldd >= a->N, "cvft_gemm: bad ldd");
     CVFT_CHECK_ARG(!a->residual || a->ldr >= a->N, "cvft_gemm: bad ldr");
     CVFT_CHECK_ARG((long)a->M * 1 < (1L << 31) && (long)(a->M / a->Tm) * a->Tin < (1L << 31), "cvft_gemm: too many rows");
-    hipStream_t st = (hipStream_t)stream;
-    return a->dtype == CVFT_F32 ? gemm_launch<float>(a, st) : gemm_launch<bf16_t>(a, st);
+    return 0;
+}
+
+// plan, then either print the plan (buf: cvft_gemm_plan) or make its launches: every hipFuncSetAttribute before the first enqueue
+template <typename T>
+static int gemm_run(const cvft_gemm_args* a, hipStream_t st, char* buf, int buflen) {
+    GemmPlan<T> plan;
+    int rc = gemm_plan<T>(a, gemm_knobs(), cvft_concurrent_chains(), plan);
+    if (rc) return rc;
+    if (buf) {
+        int used = 0;
+        for (int i = 0; i < plan.n && used < buflen; ++i) {
+            const GemmLaunch<T>& l = plan.l[i];
+            used += snprintf(buf + used, buflen - used, "%s grid=%u block=%u lds=%zu rows=%d+%d\n", l.label, l.grid, l.block, l.lds, l.p.row_off, l.p.M);
+        }
+        CVFT_CHECK_ARG(used < buflen, "cvft_gemm_plan: buffer of %d bytes is too small", buflen);
+        return 0;
+    }
+    for (int i = 0; i < plan.n; ++i)
+        if ((rc = plan.l[i].fn(plan.l[i], st, false)) != 0) return rc;
+    for (int i = 0; i < plan.n; ++i) {
+        if ((rc = plan.l[i].fn(plan.l[i], st, true)) != 0) return rc;
+        cvft_set_kernel_label("%s", plan.l[i].label);
+        CVFT_LAUNCH_CHECK("cvft_gemm");
+    }
+    return 0;
+}
+
+extern "C" int cvft_gemm(const cvft_gemm_args* a, void* stream) {
+    const int rc = gemm_check_args(a);
+    if (rc || a->M == 0) return rc;
+    return a->dtype == CVFT_F32 ? gemm_run<float>(a, (hipStream_t)stream, nullptr, 0) : gemm_run<bf16_t>(a, (hipStream_t)stream, nullptr, 0);
+}
+
+extern "C" int cvft_gemm_plan(const cvft_gemm_args* a, char* buf, int buflen) {
+    CVFT_CHECK_ARG(buf && buflen > 0, "cvft_gemm_plan: no buffer");
+    buf[0] = 0;
+    const int rc = gemm_check_args(a);
+    if (rc || a->M == 0) return rc;
+    return a->dtype == CVFT_F32 ? gemm_run<float>(a, nullptr, buf, buflen) : gemm_run<bf16_t>(a, nullptr, buf, buflen);
 }
 
 // ------------------------------------------------------------------------------

@@ -34,12 +34,12 @@ struct GP {
     // fused side path: U = lora_scale * A_tile . La^T is computed inside this launch (La [R][K], R <= 16),
     // fed to the rank-R extension step and written to Uout [M][ldu] by the n-tile-0 blocks
     const T* La; int ldla; unsigned bytesL; float lora_scale; T* Uout; int fuse;
-    int direct_epi;               // LDS-DMA kernels: register epilogue allowed (set by gemm_glds_launch)
+    int direct_epi;               // LDS-DMA kernels: register epilogue allowed (set by gemm_glds_plan / gemm_p256_plan)
     int xcd_nsplit;               // LDS-DMA kernels: XCDs across N (1 = linear tile ranges; 2/4/8 = rectangles, see kernel)
     float xdrop_p; const long long* xdrop_seed; unsigned xdrop_sites[4];      // masked rank extension (cvft.h); 0 = off
     float odrop_p; unsigned odrop_site;     // output dropout (cvft.h): C = residual + keep / (1 - p) * epi(.), seed = xdrop_seed; 0 = off
     int row_off;                  // rows in front of this launch's row 0 in the tensor the dropout masks index (a launch that computes a
-                                  // row range of a larger product: gemm_p256_launch's row split); 0 otherwise
+                                  // row range of a larger product: gemm_p256_plan's row split); 0 otherwise
 };
 
 // keep / (1 - p) factors of the output-dropout mask for the 4-element group holding flat output element `idx` (idx % 4 == 0)
@@ -266,9 +266,84 @@ __host__ __device__ constexpr int glds_wswz(int r) { return ((r >> 1) & 1) | (((
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 
-// LDS-DMA (global_load_lds) bf16 kernels for identity-geometry GEMMs; returns 1 when the shape is not eligible.
-int gemm_glds_launch(const GP<bf16_t>& p, hipStream_t st, int cfg);
-// rank-side products C[M, R<=64] = alpha * A W^T without epilogue (skinny.hip); returns 1 when not eligible.
-int skinny_launch(const GP<bf16_t>& p, hipStream_t st);
-// 256x256 tile, 8 waves, 8-phase LDS-DMA pipeline for the LLM-sized launches (gemm_p256.hip); returns 1 when not eligible.
-int gemm_p256_launch(const GP<bf16_t>& p, hipStream_t st);
+// ---------------------------------------------------------------- host side: choose the launches (plan), then make them
+// cvft_gemm plans before it enqueues: the selection code below gemm_plan (gemm.hip) is host arithmetic on the filled GP,
+// the chains hint and the knobs -- no HIP call -- and leaves one or two GemmLaunch records in enqueue order.  Everything
+// that can fail without the device having run (no kernel eligible, split-K tile count, hipFuncSetAttribute of every
+// launch) happens before the first enqueue; cvft_gemm_plan prints the same plan without a device.
+
+// Every CVFT_* environment variable that influences which GEMM kernel runs or its grid; read once per process.
+struct GemmKnobs {
+    int glds_cfg = 0;           // CVFT_GLDS_CFG      -1 = skinny / 256x256 / LDS-DMA kernels off (register-staged kernels only); experiments
+    int glds_direct = 2;        // CVFT_GLDS_DIRECT   register epilogue: 0 off, 1 only plain epilogues, 2 whenever legal
+    int glds_ns = 0;            // CVFT_GLDS_NS       forced stage count of the LDS-DMA ring (0 = by block count); experiments
+    long glds_big_t64 = 1000;   // CVFT_GLDS_BIG_T64  64x64 tiles from which the 8-wave tiles take over
+    int glds_big = 0;           // CVFT_GLDS_BIG      experiment hook: forced big-tile configuration (15 = stamped 128x128, tools/glds_stamps.py)
+    int glds_wide = -1;         // CVFT_GLDS_WIDE     96x256 one-round tile: 0 / 1 forces, -1 = unless three chains share the chip
+    int glds_rect = 1;          // CVFT_GLDS_RECT     XCD rectangle mapping of the tile order when W exceeds an XCD's L2
+    int p256 = 1;               // CVFT_P256          256x256 kernel: 0 off, 1 auto (LLM-sized launches), 2 whenever legal
+    int p256_split = 0;         // CVFT_P256_SPLIT    k-splits: 0 none, n >= 1 forced, -1 = as many as fill the chip
+    int p256_hb = 0;            // CVFT_P256_HB       forced band height of the tile order (0 = auto)
+    int p256_rowsplit = 1;      // CVFT_P256_ROWSPLIT rows past one round of tiles go to a second, LDS-DMA launch
+    int p256_stamp = 0;         // CVFT_P256_STAMP    stamped build of the plain kernel (tools/bench_p256.py)
+    int p256_slab_bf16 = 1;     // CVFT_P256_SLAB_BF16 split-K partial tiles travel as bf16
+    int p256_narrow = 0;        // CVFT_P256_NARROW   n: auto mode also takes launches of n .. 191 tiles
+    int p256_grid = -1;         // CVFT_P256_GRID     workgroups resident at once: 0 = one per item, n = at most n, -1 = auto (chains hint)
+    int skinny_mt = 0;          // CVFT_SKINNY_MT     forced 16-row tiles per skinny block (0 = by M)
+};
+const GemmKnobs& gemm_knobs();      // gemm.hip
+
+struct P256X {                  // what the 256x256 kernel needs besides GP (gemm_p256.hip)
+    int tiles_m, tiles_n;       // output tiles
+    int S;                      // k-splits per tile (1 = none)
+    int nk_total;               // K / 64
+    int hb;                     // band height of the tile order (rows of tiles walked column-major inside a band)
+    float* ws;                  // SK: [tiles][S][65536] fp32 slabs (or the same count of bf16 when slab_bf16); set at launch time
+    int slab_bf16;              // SK: partial tiles travel as bf16 (half the slab bytes); EVERY partial, the last arriver's own
+                                // included, is rounded the same way before the fp32 sum, so the result does not depend on who arrives last
+    unsigned* cnt;              // SK: [tiles] arrival tickets (zero between launches); set at launch time
+};
+
+template <typename T>
+struct GemmLaunch {
+    // launcher of the chosen kernel instantiation: enqueue == false raises its dynamic-LDS limit (once per instantiation)
+    int (*fn)(const GemmLaunch& l, hipStream_t st, bool enqueue);
+    GP<T> p;                    // adjusted for this launch: row range (row_off, M), direct_epi, xcd_nsplit
+    unsigned grid, block;
+    size_t lds;                 // dynamic LDS bytes
+    char label[96];             // what cvft_gemm_last_kernel() reports after the launch
+    P256X x; int nitems;        // 256x256 kernel only (the split-K workspace pointers are a launch-time step)
+};
+template <typename T>
+struct GemmPlan { int n; GemmLaunch<T> l[2]; };        // in enqueue order
+
+// hipFuncSetAttribute for a launch of `lds` dynamic bytes; `done` is the instantiation's own flag (a host call per launch
+// is visible in eager mode)
+inline int gemm_lds_attr(const void* kern, size_t lds, bool& done) {
+    if (lds <= 48 * 1024 || done) return 0;
+    done = true;
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) return 0;
+    cvft_set_error("cvft_gemm: hipFuncSetAttribute(%zu) failed: %s", lds, hipGetErrorString(e));
+    return -2;
+}
+
+// ---- one definition per eligibility rule; the selection sites call these
+// identity row geometry, input side: one tap, launch row m reads row m of its batch item of A, no length mask
+template <typename T> inline bool gemm_ident_in(const GP<T>& p) { return p.ntaps == 1 && p.tap_off[0] == 0 && p.in_stride == 1 && p.Tin == p.Tm && !p.in_len; }
+// ... output side: one batch item whose launch row m writes row m of C (out_len is the caller's business: the LDS-DMA
+// epilogues honour it, the 256x256 and skinny kernels do not)
+template <typename T> inline bool gemm_ident_out(const GP<T>& p) { return p.Tm == p.M && p.out_stride == 1 && p.out_off == 0; }
+// rank extension U . Bl^T on the LDS-DMA and 256x256 kernels: whole 8-wide k-steps from 16-byte rows, at most 4 rank tiles
+inline bool gemm_rank_ext_ok(const GP<bf16_t>& p) { return p.R == 0 || (p.R % 8 == 0 && p.R <= 64 && p.vecU && p.vecB); }
+// masked rank extension (xdrop) on those kernels: whole 16-wide rank tiles of a given U, masks applied in the register epilogue
+inline bool gemm_xdrop_ok(const GP<bf16_t>& p) { return p.xdrop_p <= 0.f || (p.R > 0 && p.R % 16 == 0 && !p.fuse && glds_direct_epilogue(p)); }
+
+// The planners: 0 = planned, 1 = this kernel family is not eligible for the launch, < 0 = error (cvft_last_error).
+// rank-side products C[M, R<=64] = alpha * A W^T without epilogue (skinny.hip)
+int skinny_plan(const GP<bf16_t>& p, const GemmKnobs& k, GemmLaunch<bf16_t>& l);
+// LDS-DMA (global_load_lds) bf16 kernels for identity-geometry GEMMs (gemm_glds.hip)
+int gemm_glds_plan(const GP<bf16_t>& p, const GemmKnobs& k, int chains, GemmLaunch<bf16_t>& l);
+// 256x256 tile, 8 waves, 8-phase LDS-DMA pipeline for the LLM-sized launches (gemm_p256.hip); with the row split the plan
+// is the remainder launch (gemm_glds_plan on the rows behind one round of tiles), then the 256x256 launch
+int gemm_p256_plan(const GP<bf16_t>& p, const GemmKnobs& k, int chains, GemmPlan<bf16_t>& plan);

@@ -386,78 +386,74 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_glds_kernel(GP<bf16_t> p) {
 }
 
 template <int BM, int BN, int WM, int WN, int RT, int NS, bool DE, bool DX = false>
-static int glds_launch_de(const GP<bf16_t>& p, hipStream_t st) {
-    constexpr bool FU = RT > 0;
-    size_t ring = (size_t)NS * (BM + BN + 16 * RT) * 128 + (size_t)BM * 32 * RT;
-    size_t cs = DE ? 0 : (size_t)BM * (BN + 4) * sizeof(float);        // fp32 staging tile only for the LDS epilogue
-    size_t sm = ring > cs ? ring : cs;
+static int glds_launch_de(const GemmLaunch<bf16_t>& l, hipStream_t st, bool enqueue) {
     auto kern = gemm_glds_kernel<BM, BN, WM, WN, RT, NS, DE, false, DX>;
-    static bool attr_set = false;             // per instantiation; a host call per launch is visible in eager mode
-    if (sm > 48 * 1024 && !attr_set) {
-        attr_set = true;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) {
-            cvft_set_error("cvft_gemm: hipFuncSetAttribute(%zu) failed: %s", sm, hipGetErrorString(e));
-            return -2;
-        }
-    }
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
-    long tiles = (long)tiles_m * tiles_n;
-    GP<bf16_t> q = p;
-    q.xcd_nsplit = 1;
-    {   // rectangle mapping when W does not fit an XCD's L2 and the split balances (see kernel)
-        static const int rect_on = getenv("CVFT_GLDS_RECT") ? atoi(getenv("CVFT_GLDS_RECT")) : 1;
-        const size_t wbytes = (size_t)p.N * p.K * 2;
-        if (rect_on && wbytes > (size_t)3 << 20) {
-            int cx = 2;
-            while (cx < 8 && wbytes / cx > ((size_t)2 << 20) + ((size_t)1 << 18)) cx *= 2;
-            const int cy = 8 / cx;
-            const long tn_per = (tiles_n + cx - 1) / cx, tm_per = (tiles_m + cy - 1) / cy;
-            const long padded = 8 * tn_per * tm_per;
-            if (tiles_m >= cy && padded * 100 <= tiles * 108) {          // <= 8 % idle slots
-                q.xcd_nsplit = cx;
-                tiles = padded;
-            }
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(WM * WN * 64), sm, st, q);
-    if (FU) cvft_set_kernel_label("gemm_glds_kernel<bf16,%d,%d,%d,%d,ns%d,%s>,fusedU%d", BM, BN, WM, WN, NS, DE ? "regepi" : "ldsepi", 16 * RT);
-    else cvft_set_kernel_label("gemm_glds_kernel<bf16,%d,%d,%d,%d,ns%d,%s>%s", BM, BN, WM, WN, NS, DE ? "regepi" : "ldsepi", DX ? ",xdrop" : "");
-    CVFT_LAUNCH_CHECK("cvft_gemm");
+    static bool attr_set = false;
+    if (!enqueue) return gemm_lds_attr(reinterpret_cast<const void*>(kern), l.lds, attr_set);
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.block), l.lds, st, l.p);
     return 0;
 }
 
-template <int BM, int BN, int WM, int WN, int RT = 0, int NS = 2>
-static int glds_launch_cfg(const GP<bf16_t>& p, hipStream_t st) {
-    if (p.xdrop_p > 0.f) {          // masked rank extension: register epilogue, non-fused instantiations only
-        if constexpr (RT == 0) {
-            if (glds_direct_epilogue(p)) return glds_launch_de<BM, BN, WM, WN, 0, NS, true, true>(p, st);
+// grid, LDS size, tile order and label of a launch of l.p on tile configuration <BM, BN, WM, WN, RT, NS>, epilogue de / dx
+static void glds_fill(GemmLaunch<bf16_t>& l, const GemmKnobs& k, int BM, int BN, int WM, int WN, int RT, int NS, bool de, bool dx) {
+    GP<bf16_t>& p = l.p;
+    const size_t ring = (size_t)NS * (BM + BN + 16 * RT) * 128 + (size_t)BM * 32 * RT;
+    const size_t cs = de ? 0 : (size_t)BM * (BN + 4) * sizeof(float);        // fp32 staging tile only for the LDS epilogue
+    l.lds = ring > cs ? ring : cs;
+    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    long tiles = (long)tiles_m * tiles_n;
+    p.xcd_nsplit = 1;
+    const size_t wbytes = (size_t)p.N * p.K * 2;
+    if (k.glds_rect && wbytes > (size_t)3 << 20) {   // rectangle mapping when W does not fit an XCD's L2 and the split balances (see kernel)
+        int cx = 2;
+        while (cx < 8 && wbytes / cx > ((size_t)2 << 20) + ((size_t)1 << 18)) cx *= 2;
+        const int cy = 8 / cx;
+        const long tn_per = (tiles_n + cx - 1) / cx, tm_per = (tiles_m + cy - 1) / cy;
+        const long padded = 8 * tn_per * tm_per;
+        if (tiles_m >= cy && padded * 100 <= tiles * 108) {          // <= 8 % idle slots
+            p.xcd_nsplit = cx;
+            tiles = padded;
         }
-        return 1;
     }
-    if (glds_direct_epilogue(p)) return glds_launch_de<BM, BN, WM, WN, RT, NS, true>(p, st);
-    return glds_launch_de<BM, BN, WM, WN, RT, NS, false>(p, st);
+    l.grid = (unsigned)tiles; l.block = WM * WN * 64;
+    if (RT > 0) snprintf(l.label, sizeof(l.label), "gemm_glds_kernel<bf16,%d,%d,%d,%d,ns%d,%s>,fusedU%d", BM, BN, WM, WN, NS, de ? "regepi" : "ldsepi", 16 * RT);
+    else snprintf(l.label, sizeof(l.label), "gemm_glds_kernel<bf16,%d,%d,%d,%d,ns%d,%s>%s", BM, BN, WM, WN, NS, de ? "regepi" : "ldsepi", dx ? ",xdrop" : "");
+}
+
+template <int BM, int BN, int WM, int WN, int RT = 0, int NS = 2>
+static int glds_plan_cfg(GemmLaunch<bf16_t>& l, const GemmKnobs& k) {
+    const bool de = glds_direct_epilogue(l.p), dx = l.p.xdrop_p > 0.f;
+    if (dx) {                       // masked rank extension: register epilogue, non-fused instantiations only (gemm_xdrop_ok has checked)
+        if constexpr (RT == 0) l.fn = glds_launch_de<BM, BN, WM, WN, 0, NS, true, true>;
+        else return 1;
+    } else if (de) l.fn = glds_launch_de<BM, BN, WM, WN, RT, NS, true>;
+    else l.fn = glds_launch_de<BM, BN, WM, WN, RT, NS, false>;
+    glds_fill(l, k, BM, BN, WM, WN, RT, NS, de, dx);
+    return 0;
+}
+
+// stamped build of the default 128x128 kernel (register epilogue): CVFT_GLDS_BIG=15, tools/glds_stamps.py
+static int glds_launch_stamped(const GemmLaunch<bf16_t>& l, hipStream_t st, bool enqueue) {
+    auto kern = gemm_glds_kernel<128, 128, 4, 2, 0, 2, true, true>;
+    static bool attr_set = false;
+    if (!enqueue) return gemm_lds_attr(reinterpret_cast<const void*>(kern), l.lds, attr_set);
+    hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.block), l.lds, st, l.p);
+    return 0;
 }
 
 // Returns 1 when the launch is not eligible (the caller falls back to gemm.hip's register-staged kernel).
-int gemm_glds_launch(const GP<bf16_t>& p_in, hipStream_t st, int cfg) {
-    static const int direct_mode = getenv("CVFT_GLDS_DIRECT") ? atoi(getenv("CVFT_GLDS_DIRECT")) : 2;   // 0 off, 1 only plain epilogues, 2 whenever legal
-    if (cfg != -256) {   // LLM-sized launches: 256x256 tile on the 8-phase pipeline (gemm_p256.hip; -256 = its own remainder launch)
-        const int rc = gemm_p256_launch(p_in, st);
-        if (rc != 1) return rc;
-    }
-    GP<bf16_t> p = p_in;
+int gemm_glds_plan(const GP<bf16_t>& p_in, const GemmKnobs& k, int chains, GemmLaunch<bf16_t>& l) {
+    GP<bf16_t>& p = l.p;
+    p = p_in;
     const bool simple = !p.preact && !p.dact_src && !p.residual;
-    p.direct_epi = direct_mode == 2 || (direct_mode == 1 && simple);
-    const bool ident = p.ntaps == 1 && p.tap_off[0] == 0 && p.in_stride == 1 && p.Tin == p.Tm && !p.in_len;
-    if (!ident || p.K % 64 != 0 || !p.vecA || !p.vecW || p.N <= 32) return 1;
+    p.direct_epi = k.glds_direct == 2 || (k.glds_direct == 1 && simple);
+    // input side only: the epilogues handle batched / strided / masked output rows
+    if (!gemm_ident_in(p) || p.K % 64 != 0 || !p.vecA || !p.vecW || p.N <= 32 || !gemm_xdrop_ok(p)) return 1;
     const long t64 = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
     // Stage count: a deep DMA pipeline only pays while the CU still holds every block that wants to run there
     // (16 / 24 KB per stage), measured on cold operands (tools/bench_cold.py): <= 2 blocks per CU and >= 4 k-tiles ->
     // 4 stages (64x64) / 3 (128x64); a third block per CU -> 3; beyond that 2.  CVFT_GLDS_NS overrides (experiments).
-    static const int ns_env = getenv("CVFT_GLDS_NS") ? atoi(getenv("CVFT_GLDS_NS")) : 0;
-    static const long big_thr = getenv("CVFT_GLDS_BIG_T64") ? atol(getenv("CVFT_GLDS_BIG_T64")) : 1000;
-    const bool big = t64 >= big_thr;
+    const bool big = t64 >= k.glds_big_t64;
     const long blocks = big ? (long)((p.M + 127) / 128) * ((p.N + 63) / 64) : t64;
     const int nk = p.K / 64;
     int ns = 2;
@@ -465,52 +461,48 @@ int gemm_glds_launch(const GP<bf16_t>& p_in, hipStream_t st, int cfg) {
         if (big) ns = blocks <= 512 ? 3 : 2;
         else ns = blocks <= 512 ? 4 : (blocks <= 768 ? 3 : 2);
     }
-    if (ns_env) ns = ns_env;
-    if (p.fuse) {     // gemm_launch has already checked the La / Bl alignment
-        if (p.R < 1 || p.R > 48 || p.Tm != p.M || p.out_stride != 1 || p.out_off != 0) return 1;
+    if (k.glds_ns) ns = k.glds_ns;
+    if (p.fuse) {     // gemm_plan has already checked the La / Bl alignment; Uout rows are launch rows (output side identity), R <= 48: three rank tiles
+        if (p.R < 1 || p.R > 48 || !gemm_ident_out(p)) return 1;
         if (p.R > 16) {                                          // stacked q|k|v adapters: three rank tiles
             if (p.R % 8 != 0) return 1;
             if (big) {
-                if (ns >= 3) return glds_launch_cfg<128, 64, 4, 2, 3, 3>(p, st);
-                return glds_launch_cfg<128, 64, 4, 2, 3, 2>(p, st);
+                if (ns >= 3) return glds_plan_cfg<128, 64, 4, 2, 3, 3>(l, k);
+                return glds_plan_cfg<128, 64, 4, 2, 3, 2>(l, k);
             }
-            if (ns >= 4) return glds_launch_cfg<64, 64, 2, 2, 3, 4>(p, st);
-            if (ns == 3) return glds_launch_cfg<64, 64, 2, 2, 3, 3>(p, st);
-            return glds_launch_cfg<64, 64, 2, 2, 3, 2>(p, st);
+            if (ns >= 4) return glds_plan_cfg<64, 64, 2, 2, 3, 4>(l, k);
+            if (ns == 3) return glds_plan_cfg<64, 64, 2, 2, 3, 3>(l, k);
+            return glds_plan_cfg<64, 64, 2, 2, 3, 2>(l, k);
         }
         if (big) {
-            if (ns >= 3) return glds_launch_cfg<128, 64, 4, 2, 1, 3>(p, st);
-            return glds_launch_cfg<128, 64, 4, 2, 1, 2>(p, st);
+            if (ns >= 3) return glds_plan_cfg<128, 64, 4, 2, 1, 3>(l, k);
+            return glds_plan_cfg<128, 64, 4, 2, 1, 2>(l, k);
         }
-        if (ns >= 4) return glds_launch_cfg<64, 64, 2, 2, 1, 4>(p, st);
-        if (ns == 3) return glds_launch_cfg<64, 64, 2, 2, 1, 3>(p, st);
-        return glds_launch_cfg<64, 64, 2, 2, 1, 2>(p, st);
+        if (ns >= 4) return glds_plan_cfg<64, 64, 2, 2, 1, 4>(l, k);
+        if (ns == 3) return glds_plan_cfg<64, 64, 2, 2, 1, 3>(l, k);
+        return glds_plan_cfg<64, 64, 2, 2, 1, 2>(l, k);
     }
-    if (p.R > 0 && (p.R % 8 != 0 || p.R > 64 || !p.vecU || !p.vecB)) return 1;
+    if (!gemm_rank_ext_ok(p)) return 1;
     // measured on MI355X (tools/sweep_gemm.py): 128x64 x 8 waves once there are >= 4 64x64 tiles per CU, else 64x64
-    static const int big_env = getenv("CVFT_GLDS_BIG") ? atoi(getenv("CVFT_GLDS_BIG")) : 0;     // experiment hook
+    const int big_env = k.glds_big;     // experiment hook
     if (big && big_env && nk >= 8 && t64 >= 1024) {
         switch (big_env) {
-            case 1: return glds_launch_cfg<128, 128, 2, 2, 0, 3>(p, st);
-            case 3: return glds_launch_cfg<128, 128, 2, 4, 0, 3>(p, st);
-            case 4: return glds_launch_cfg<256, 128, 4, 2, 0, 2>(p, st);
-            case 6: return glds_launch_cfg<128, 128, 2, 2, 0, 2>(p, st);
-            case 8: return glds_launch_cfg<128, 128, 2, 4, 0, 2>(p, st);
-            case 17: return glds_launch_cfg<128, 256, 4, 4, 0, 3>(p, st);
-            case 19: return glds_launch_cfg<96, 256, 3, 4, 0, 3>(p, st);
-            case 13: return glds_launch_cfg<128, 128, 4, 2, 0, 3>(p, st);
-            case 14: return glds_launch_cfg<128, 128, 4, 2, 0, 4>(p, st);
-            case 15: {          // stamped build of the default 128x128 kernel (register epilogue)
-                auto kern = gemm_glds_kernel<128, 128, 4, 2, 0, 2, true, true>;
-                hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-                GP<bf16_t> q = p;
-                q.xcd_nsplit = 1;
-                hipLaunchKernelGGL(kern, dim3((unsigned)(((p.M + 127) / 128) * ((p.N + 127) / 128))), dim3(512), 65536, st, q);
-                cvft_set_kernel_label("gemm_glds_kernel<bf16,128,128,4,2,ns2,regepi,stamped>");
+            case 1: return glds_plan_cfg<128, 128, 2, 2, 0, 3>(l, k);
+            case 3: return glds_plan_cfg<128, 128, 2, 4, 0, 3>(l, k);
+            case 4: return glds_plan_cfg<256, 128, 4, 2, 0, 2>(l, k);
+            case 6: return glds_plan_cfg<128, 128, 2, 2, 0, 2>(l, k);
+            case 8: return glds_plan_cfg<128, 128, 2, 4, 0, 2>(l, k);
+            case 17: return glds_plan_cfg<128, 256, 4, 4, 0, 3>(l, k);
+            case 19: return glds_plan_cfg<96, 256, 3, 4, 0, 3>(l, k);
+            case 13: return glds_plan_cfg<128, 128, 4, 2, 0, 3>(l, k);
+            case 14: return glds_plan_cfg<128, 128, 4, 2, 0, 4>(l, k);
+            case 15:
+                p.xcd_nsplit = 1;
+                l.fn = glds_launch_stamped; l.grid = (unsigned)(((p.M + 127) / 128) * ((p.N + 127) / 128)); l.block = 512; l.lds = 65536;
+                snprintf(l.label, sizeof(l.label), "gemm_glds_kernel<bf16,128,128,4,2,ns2,regepi,stamped>");
                 return 0;
-            }
-            case 11: if (ns >= 3) return glds_launch_cfg<128, 64, 4, 2, 0, 3>(p, st);
-                     return glds_launch_cfg<128, 64, 4, 2, 0, 2>(p, st);
+            case 11: if (ns >= 3) return glds_plan_cfg<128, 64, 4, 2, 0, 3>(l, k);
+                     return glds_plan_cfg<128, 64, 4, 2, 0, 2>(l, k);
             default: break;
         }
     }
@@ -534,20 +526,19 @@ int gemm_glds_launch(const GP<bf16_t>& p_in, hipStream_t st, int cfg) {
     // ... when this chain has the chip to itself: the 96x256 tile owns its CU (12 waves, 135 KB of LDS), so with other chains in
     // flight (joint mode: LLM + 2 x Flow) their workgroups wait for whole CUs to drain; two co-residing 128x128 blocks per CU are
     // slower alone and faster in the step (same-box A/B, joint B = 16: 23.62 -> 23.16 ms, 22.70 on a second box).  CVFT_GLDS_WIDE=0/1 forces.
-    static const int wide_env = getenv("CVFT_GLDS_WIDE") ? atoi(getenv("CVFT_GLDS_WIDE")) : -1;
-    const int wide_on = wide_env >= 0 ? wide_env : (cvft_concurrent_chains() >= 3 ? 0 : 1);
+    const int wide_on = k.glds_wide >= 0 ? k.glds_wide : (chains >= 3 ? 0 : 1);
     if (big && wide_on && nk >= 8 && t64 >= 1000 && p.N >= 256 && (long)((p.M + 95) / 96) * ((p.N + 255) / 256) <= 256)
-        return glds_launch_cfg<96, 256, 3, 4, 0, 3>(p, st);
-    if (big && (nk >= 8 || big_env == 12) && t64 >= 1000) return glds_launch_cfg<128, 128, 4, 2, 0, 2>(p, st);
+        return glds_plan_cfg<96, 256, 3, 4, 0, 3>(l, k);
+    if (big && (nk >= 8 || big_env == 12) && t64 >= 1000) return glds_plan_cfg<128, 128, 4, 2, 0, 2>(l, k);
     if (big) {
-        if (ns >= 3) return glds_launch_cfg<128, 64, 4, 2, 0, 3>(p, st);
-        return glds_launch_cfg<128, 64, 4, 2, 0, 2>(p, st);
+        if (ns >= 3) return glds_plan_cfg<128, 64, 4, 2, 0, 3>(l, k);
+        return glds_plan_cfg<128, 64, 4, 2, 0, 2>(l, k);
     }
     // 64x64 x 4 waves stays the best small tile: 128x64 / 64x128 with 4 waves (64x32 wave tiles) measured 10-40 % slower on
     // the estimator / encoder shapes (M = 4000..4640, N = 256..1536), where block count matters more than issue efficiency
-    if (ns >= 4) return glds_launch_cfg<64, 64, 2, 2, 0, 4>(p, st);
-    if (ns == 3) return glds_launch_cfg<64, 64, 2, 2, 0, 3>(p, st);
-    return glds_launch_cfg<64, 64, 2, 2, 0, 2>(p, st);
+    if (ns >= 4) return glds_plan_cfg<64, 64, 2, 2, 0, 4>(l, k);
+    if (ns == 3) return glds_plan_cfg<64, 64, 2, 2, 0, 3>(l, k);
+    return glds_plan_cfg<64, 64, 2, 2, 0, 2>(l, k);
 }
 
 extern "C" int cvft_debug_glds_stamps(unsigned long long* host_out) {

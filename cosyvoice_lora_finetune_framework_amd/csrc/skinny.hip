@@ -81,33 +81,36 @@ __global__ void __launch_bounds__(512) skinny_kernel(int M, int K, const bf16_t*
     }
 }
 
+template <int RB, int MT, int KS>
+static int skinny_launch_t(const GemmLaunch<bf16_t>& l, hipStream_t st, bool enqueue) {
+    const GP<bf16_t>& p = l.p;
+    if (enqueue) hipLaunchKernelGGL((skinny_kernel<RB, MT, KS>), dim3(l.grid), dim3(l.block), 0, st, p.M, p.K, p.A, p.lda, p.W, p.ldw, p.alpha, p.C, p.ldc);
+    return 0;
+}
+
 // returns 1 when the launch is not a plain skinny product
-int skinny_launch(const GP<bf16_t>& p, hipStream_t st) {
-    const bool ident = p.ntaps == 1 && p.tap_off[0] == 0 && p.in_stride == 1 && p.Tin == p.Tm && !p.in_len && p.Tm == p.M &&
-                       p.out_stride == 1 && p.out_off == 0 && !p.out_len;
-    if (!ident || p.fuse || p.R > 0 || p.bias || p.act || p.preact || p.dact_src || p.residual) return 1;
+int skinny_plan(const GP<bf16_t>& p, const GemmKnobs& k, GemmLaunch<bf16_t>& l) {
+    // both sides and no out_len: the kernel writes launch row m to row m of C, nothing else
+    if (!gemm_ident_in(p) || !gemm_ident_out(p) || p.out_len || p.fuse || p.R > 0 || p.bias || p.act || p.preact || p.dact_src || p.residual) return 1;
     if (p.N > 64 || p.N % 16 != 0 || p.K % 32 != 0 || p.K < 32 || !p.vecA || !p.vecW) return 1;
     // rows per block: 32 (every A fragment used twice) unless that leaves half the chip without a block -- measured
     // (tools/bench_side.py, cold): M = 4000, K = 1536, R = 48: 12.3 us at 32 rows (125 blocks), 10.0 at 16 (250), 16.6 at 64;
     // from M = 5376 up 16 rows lose (20.2 -> 25.7 us at K = 3072: A is re-read from L2 once per block)
-    static const int mt_forced = getenv("CVFT_SKINNY_MT") ? atoi(getenv("CVFT_SKINNY_MT")) : 0;
-    const int mt_env = mt_forced ? mt_forced : (p.M <= 4096 ? 1 : 2);
+    const int mt_env = k.skinny_mt ? k.skinny_mt : (p.M <= 4096 ? 1 : 2);
+    const int mt = mt_env == 1 ? 1 : (mt_env == 4 ? 4 : 2);
     const int ksteps_per_wave = (p.K / 32 + 7) / 8;
-#define SK_LAUNCH(RBv, MTv, KSv) hipLaunchKernelGGL((skinny_kernel<RBv, MTv, KSv>), dim3((p.M + 16 * MTv - 1) / (16 * MTv)), dim3(512), 0, st, p.M, p.K, p.A, p.lda, p.W, p.ldw, \
-                                               p.alpha, p.C, p.ldc)
-#define SK_KS(RBv, MTv) do { if (ksteps_per_wave >= 4) SK_LAUNCH(RBv, MTv, 4); else if (ksteps_per_wave >= 2) SK_LAUNCH(RBv, MTv, 2); else SK_LAUNCH(RBv, MTv, 1); } while (0)
-#define SK_RB(RBv) do { if (mt_env == 1) SK_KS(RBv, 1); else if (mt_env == 4) SK_KS(RBv, 4); else SK_KS(RBv, 2); } while (0)
+#define SK_KS(RBv, MTv) (ksteps_per_wave >= 4 ? skinny_launch_t<RBv, MTv, 4> : ksteps_per_wave >= 2 ? skinny_launch_t<RBv, MTv, 2> : skinny_launch_t<RBv, MTv, 1>)
+#define SK_RB(RBv) (mt == 1 ? SK_KS(RBv, 1) : mt == 4 ? SK_KS(RBv, 4) : SK_KS(RBv, 2))
     switch (p.N / 16) {
-        case 1: SK_RB(1); break;
-        case 2: SK_RB(2); break;
-        case 3: SK_RB(3); break;
-        default: SK_RB(4); break;
+        case 1: l.fn = SK_RB(1); break;
+        case 2: l.fn = SK_RB(2); break;
+        case 3: l.fn = SK_RB(3); break;
+        default: l.fn = SK_RB(4); break;
     }
 #undef SK_RB
 #undef SK_KS
-#undef SK_LAUNCH
-    cvft_set_kernel_label("skinny_kernel<bf16,r%d>", p.N);
-    CVFT_LAUNCH_CHECK("cvft_gemm");
+    l.p = p; l.grid = (unsigned)((p.M + 16 * mt - 1) / (16 * mt)); l.block = 512; l.lds = 0;
+    snprintf(l.label, sizeof(l.label), "skinny_kernel<bf16,r%d>", p.N);
     return 0;
 }
 
@@ -367,7 +370,7 @@ extern "C" int cvft_ln_skinny_dropout(int M, int K, int R, const void* X, const 
     uint4 st = make_uint4(sites[0], nt > 1 ? sites[1] : 0u, nt > 2 ? sites[2] : 0u, 0u);
     const LnArgs ln = {gamma, beta, eps, (bf16_t*)Y, mean, rstd};
     // 16 rows per block while 32 would leave half the chip without a block (the estimator's half batches), like skinny_launch
-    static const int mt_forced = getenv("CVFT_SKINNY_MT") ? atoi(getenv("CVFT_SKINNY_MT")) : 0;
+    const int mt_forced = gemm_knobs().skinny_mt;
     const int mt = mt_forced ? mt_forced : (M <= 4096 ? 1 : 2);
 #define LSK_LAUNCH(RBv, MTv, KSv) hipLaunchKernelGGL((skinny_dropout_kernel<RBv, MTv, KSv, false, true>), dim3((M + 16 * MTv - 1) / (16 * MTv)), dim3(512), 0, \
                                            (hipStream_t)stream, M, K,                                                                           \

@@ -113,6 +113,7 @@ SIGNATURES = {
     "cvft_concurrent_chains": [],
     "cvft_last_error": [],
     "cvft_gemm": [C.POINTER(GemmArgs), _p],
+    "cvft_gemm_plan": [C.POINTER(GemmArgs), C.c_char_p, _i],
     "cvft_gemm_last_kernel": [],
     "cvft_tn_accum": [_i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p],
     "cvft_lora_rank_accum": [_i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _p],

@@ -99,6 +99,13 @@ typedef struct {
 } cvft_gemm_args;
 
 int cvft_gemm(const cvft_gemm_args* a, void* stream);
+/* What cvft_gemm(a, .) would launch, without launching it (version >= 102): same argument checks, return codes and
+ * cvft_last_error() text as cvft_gemm; on success `buf` holds one line per launch, in enqueue order,
+ *   "<label> grid=<workgroups> block=<threads> lds=<dynamic LDS bytes> rows=<first row>+<row count>\n"
+ * (no line for M == 0).  The last line's label is what cvft_gemm_last_kernel() reports after the real call.  The choice
+ * depends on the arguments, cvft_concurrent_chains() and the CVFT_* knobs of the process.  Operand pointers are only looked at
+ * for NULL and 16-byte alignment, never dereferenced, and no HIP call is made: it runs on a machine without a GPU. */
+int cvft_gemm_plan(const cvft_gemm_args* a, char* buf, int buflen);
 
 /* fp8 path for the frozen-W GEMMs (BASELINE configs[4]) -- OCP e4m3 operands, fp32 accumulation:
  *   cvft_quant_fp8_rows : q[m][k] = e4m3(x[m][k] / s[m]),  s[m] = max_k |x[m][k]| / 448   (bf16 in; activation rows = per-token

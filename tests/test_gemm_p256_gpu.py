@@ -33,7 +33,7 @@ WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "p256_worker.p
 
 
 def split_rows(M, N):
-    """rows the 256x256 kernel computes itself under default knobs: gemm_p256_launch's row split (256 < tiles <= 416)
+    """rows the 256x256 kernel computes itself under default knobs: gemm_p256_plan's row split (256 < tiles <= 416)
     hands the tile rows behind the first 256 / tiles_n to a 128-row remainder launch"""
     tm, tn = -(-M // 256), N // 256
     if 256 < tm * tn <= 416 and 1 <= 256 // tn < tm:

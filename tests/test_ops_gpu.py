@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from dispatch_fixture import plan_lines, planned
 from helpers import keep_scale_host as _keep_scale_host
 
 pytestmark = pytest.mark.gpu
@@ -62,9 +63,11 @@ def test_gemm_tile_configs_and_epilogue_forms(M, N, K, r, label):
     u = q(rnd(M, r, seed=3), dtype) if r else None
     bl = q(rnd(N, r, seed=4) * 0.1, dtype) if r else None
     pre = torch.empty(M, N, device=DEV, dtype=dtype)
-    y = HF.gemm(x.to(DEV, dtype), w.to(DEV, dtype), bias=b.to(DEV), U=None if u is None else u.to(DEV, dtype),
-                Bl=None if bl is None else bl.to(DEV, dtype), act="gelu_erf", preact=pre, residual=res.to(DEV, dtype))
+    with planned(HF.lib()) as plans:
+        y = HF.gemm(x.to(DEV, dtype), w.to(DEV, dtype), bias=b.to(DEV), U=None if u is None else u.to(DEV, dtype),
+                    Bl=None if bl is None else bl.to(DEV, dtype), act="gelu_erf", preact=pre, residual=res.to(DEV, dtype))
     assert label in HF.lib().cvft_gemm_last_kernel().decode(), HF.lib().cvft_gemm_last_kernel().decode()
+    assert plans[0][0] == 0 and plan_lines(plans[0][1])[-1][0] == HF.lib().cvft_gemm_last_kernel().decode(), plans     # named before the launch
     z = x.double() @ w.double().t() + b.double()
     if r:
         z = z + u.double() @ bl.double().t()
