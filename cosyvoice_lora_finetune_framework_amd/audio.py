@@ -1,0 +1,185 @@
+"""Waveform -> the Flow's log-mel features on the GPU: the drop-in for the reference's ``matcha/utils/audio.py``.
+
+``mel_spectrogram`` keeps the reference's signature and layout ([B, 80, T]); ``MelExtractor`` is what the other callers
+use (ragged batches, channel-last output, padding value).  Both run ``cvft_melspec`` (csrc/melspec.hip): one launch from
+samples to log-mel.  Only the CosyVoice-300M setting is built -- 22 050 Hz, n_fft = window = 1024, hop 256, 80 Slaney
+bands over 0 .. 8000 Hz, ``center=False`` -- and every other setting raises ``NotImplementedError`` naming it.
+Resampling is not built: audio at another rate raises.
+
+``mel_filterbank`` restates the documented formula of ``librosa.filters.mel`` with its defaults (Slaney scale, Slaney
+area normalisation) in fp64, rounded once to fp32; it is not a copy of librosa's output.
+"""
+from __future__ import annotations
+
+import math
+import wave
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+SAMPLE_RATE, N_FFT, HOP, WIN, N_MELS, FMIN, FMAX = 22050, 1024, 256, 1024, 80, 0, 8000
+REFLECT = (N_FFT - HOP) // 2                 # samples of reflect padding per side
+MIN_SAMPLES = REFLECT + 1
+LOG_CLAMP = math.log(1e-5)                   # the log-mel of digital silence
+
+_MIN_LOG_HZ = 1000.0
+_MIN_LOG_MEL = 15.0                           # 1000 Hz / (200/3 Hz per mel)
+_LOGSTEP = math.log(6.4) / 27.0
+
+
+def hz_to_mel(f):
+    """Slaney scale: linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mel per factor 6.4)."""
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f >= _MIN_LOG_HZ, _MIN_LOG_MEL + np.log(np.maximum(f, 1e-300) / _MIN_LOG_HZ) / _LOGSTEP, f * 3.0 / 200.0)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= _MIN_LOG_MEL, _MIN_LOG_HZ * np.exp(_LOGSTEP * (m - _MIN_LOG_MEL)), m * 200.0 / 3.0)
+
+
+def mel_frequencies(n: int, fmin: float, fmax: float) -> np.ndarray:
+    """n frequencies (Hz) equally spaced on the mel scale from fmin to fmax."""
+    return mel_to_hz(np.linspace(float(hz_to_mel(fmin)), float(hz_to_mel(fmax)), n))
+
+
+def mel_filterbank(sr: int, n_fft: int, n_mels: int, fmin: float, fmax: Optional[float]) -> np.ndarray:
+    """[n_mels, n_fft // 2 + 1] fp32: triangles between neighbouring mel frequencies, row i scaled by
+    2 / (f[i+2] - f[i])."""
+    fmax = sr / 2.0 if fmax is None else float(fmax)
+    bins = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
+    f = mel_frequencies(n_mels + 2, fmin, fmax)
+    fdiff = np.diff(f)
+    ramps = f[:, None] - bins[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    w = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (f[2:] - f[:-2]))[:, None]
+    return w.astype(np.float32)
+
+
+def n_frames(length: int) -> int:
+    """frames of a `length`-sample waveform: (length + 2 * 384 - 1024) // 256 + 1 == length // 256."""
+    return int(length) // HOP
+
+
+def pack_dft_table(nchunks: int) -> np.ndarray:
+    """the DFT operand of cvft_melspec (include/cvft.h): hann[n] * cos | sin(2 pi (n k mod 1024) / 1024) in fp64, rounded
+    once, [chunk][step][cos | sin][lane][e] with k = 16 c + (l & 15), n = 256 (s >> 4) + 64 (l >> 4) + 4 (s & 15) + e."""
+    c = np.arange(nchunks).reshape(-1, 1, 1, 1)
+    s = np.arange(64).reshape(1, -1, 1, 1)
+    lane = np.arange(64).reshape(1, 1, -1, 1)
+    e = np.arange(4).reshape(1, 1, 1, -1)
+    k = 16 * c + (lane & 15)
+    n = 256 * (s >> 4) + 64 * (lane >> 4) + 4 * (s & 15) + e
+    hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / WIN)                  # periodic Hann
+    ang = 2.0 * np.pi * ((n * k) % N_FFT) / N_FFT
+    live = k <= N_FFT // 2
+    tab = np.stack([np.where(live, hann * np.cos(ang), 0.0), np.where(live, hann * np.sin(ang), 0.0)], axis=2)
+    return np.ascontiguousarray(tab.astype(np.float32))               # [nchunks, 64, 2, 64, 4]
+
+
+def pack_basis(basis: np.ndarray, nchunks: int) -> np.ndarray:
+    """the filterbank operand of cvft_melspec: [chunk][band tile][lane][i] = basis[16 m + (l & 15)][16 c + 4 (l >> 4) + i]."""
+    nb, nbin = basis.shape
+    mt = (nb + 15) // 16
+    full = np.zeros((16 * mt, 16 * nchunks), dtype=np.float32)
+    full[:nb, :min(nbin, 16 * nchunks)] = basis[:, :16 * nchunks]
+    c = np.arange(nchunks).reshape(-1, 1, 1, 1)
+    m = np.arange(mt).reshape(1, -1, 1, 1)
+    lane = np.arange(64).reshape(1, 1, -1, 1)
+    i = np.arange(4).reshape(1, 1, 1, -1)
+    return np.ascontiguousarray(full[16 * m + (lane & 15), 16 * c + 4 * (lane >> 4) + i])
+
+
+def live_bins(basis: np.ndarray) -> int:
+    """bins that carry filterbank weight: the last non-zero column + 1 (372 of 513 with the top band at 8 kHz)."""
+    return int(np.nonzero(basis.any(axis=0))[0][-1]) + 1
+
+
+def check_rate(rate: int) -> None:
+    if int(rate) != SAMPLE_RATE:
+        raise NotImplementedError(f"sampling rate {rate} Hz: only {SAMPLE_RATE} Hz audio is built (resampling is not)")
+
+
+def load_wav(path: str) -> Tuple[torch.Tensor, int]:
+    """16-bit PCM file -> (float32 samples [L] scaled by 1 / 32768, channels averaged; the file's rate)."""
+    with wave.open(path, 'rb') as f:
+        if f.getsampwidth() != 2:
+            raise NotImplementedError(f"{path}: {8 * f.getsampwidth()}-bit samples (only 16-bit PCM is read)")
+        rate, ch = f.getframerate(), f.getnchannels()
+        pcm = np.frombuffer(f.readframes(f.getnframes()), dtype='<i2')
+    x = pcm.astype(np.float32) / 32768.0
+    if ch > 1:
+        x = x.reshape(-1, ch).mean(axis=1, dtype=np.float32)
+    return torch.from_numpy(np.ascontiguousarray(x)), rate
+
+
+class MelExtractor:
+    """Holds the packed DFT table and filterbank on `device` once; ``__call__`` is one kernel launch."""
+
+    def __init__(self, device: Union[str, torch.device] = 'cuda'):
+        self.device = torch.device(device)
+        self.basis = mel_filterbank(SAMPLE_RATE, N_FFT, N_MELS, FMIN, FMAX)
+        self.nchunks = (live_bins(self.basis) + 15) // 16
+        self.dft_tab = torch.from_numpy(pack_dft_table(self.nchunks)).to(self.device)
+        self.basis_tab = torch.from_numpy(pack_basis(self.basis, self.nchunks)).to(self.device)
+
+    def __call__(self, wav: torch.Tensor, lengths: Optional[Sequence[int]] = None, channel_last: bool = False,
+                 pad_value: float = LOG_CLAMP, *, sample_rate: Optional[int] = None) -> torch.Tensor:
+        """wav [B, Lmax] (or [L]) fp32 in [-1, 1] on the device, `lengths` the rows' sample counts (default: Lmax each)
+        -> log-mel [B, 80, Tmax], or [B, Tmax, 80] with `channel_last`; Tmax = max(lengths) // 256, row b has
+        lengths[b] // 256 frames and `pad_value` after them."""
+        from .hipops import functional as HF
+        if sample_rate is not None:
+            check_rate(sample_rate)
+        if wav.dim() == 1:
+            wav = wav.unsqueeze(0)
+        if wav.dim() != 2:
+            raise ValueError(f"wav must be [B, L] or [L], got {tuple(wav.shape)}")
+        B, Lmax = wav.shape
+        lens = [Lmax] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if len(lens) != B:
+            raise ValueError(f"{len(lens)} lengths for {B} rows")
+        for i, n in enumerate(lens):
+            if n < MIN_SAMPLES or n > Lmax:
+                raise ValueError(f"row {i}: {n} samples outside [{MIN_SAMPLES}, {Lmax}] (reflect padding reads "
+                                 f"{REFLECT} samples past each end)")
+        return HF.melspec(wav, lens, self.dft_tab, self.basis_tab, self.nchunks, n_frames(max(lens)), channel_last,
+                          float(pad_value))
+
+
+_EXTRACTORS = {}
+
+
+def extractor(device) -> MelExtractor:
+    """one MelExtractor per device, built on first use."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if device not in _EXTRACTORS:
+        _EXTRACTORS[device] = MelExtractor(device)
+    return _EXTRACTORS[device]
+
+
+def check_settings(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center) -> None:
+    check_rate(sampling_rate)
+    for name, got, built in (("n_fft", n_fft, N_FFT), ("num_mels", num_mels, N_MELS), ("hop_size", hop_size, HOP),
+                             ("win_size", win_size, WIN), ("fmin", fmin, FMIN), ("center", bool(center), False)):
+        if got != built:
+            raise NotImplementedError(f"mel_spectrogram: {name}={got} (only {name}={built} is built)")
+    if fmax is not None and fmax > sampling_rate / 2:
+        raise NotImplementedError(f"mel_spectrogram: fmax={fmax} is above Nyquist ({sampling_rate / 2} Hz)")
+    if fmax != FMAX:
+        raise NotImplementedError(f"mel_spectrogram: fmax={fmax} (only fmax={FMAX} is built)")
+
+
+def mel_spectrogram(y: torch.Tensor, n_fft: int = N_FFT, num_mels: int = N_MELS, sampling_rate: int = SAMPLE_RATE,
+                    hop_size: int = HOP, win_size: int = WIN, fmin: float = FMIN, fmax: Optional[float] = FMAX,
+                    center: bool = False) -> torch.Tensor:
+    """matcha/utils/audio.py:45-82: y [B, L] on the device -> log-mel [B, num_mels, L // hop_size] fp32."""
+    check_settings(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center)
+    from .hipops.binding import CvftError
+    if not y.is_cuda:
+        raise CvftError("mel_spectrogram needs a ROCm device tensor; there is no CPU fallback")
+    return extractor(y.device)(y)

@@ -2368,3 +2368,18 @@ class DwConvFn(torch.autograd.Function):
 def dwconv1d(x, w, bias, B: int, T: int, pad_left: int, length=None):
     """x [B*T, C] channel-last, w [C, Kw] fp32; input frames t >= length[b] are treated as zero."""
     return DwConvFn.apply(x, w, bias, B, T, pad_left, length)
+
+
+def melspec(wav: torch.Tensor, lengths: Sequence[int], dft_tab: torch.Tensor, basis_tab: torch.Tensor, nchunks: int,
+            Tmax: int, channel_last: bool = False, pad_value: float = -11.512925464970229) -> torch.Tensor:
+    """cvft_melspec: wav [B, Lmax] fp32 with per-row sample counts -> log-mel [B, 80, Tmax] (or [B, Tmax, 80]); the
+    tables come from audio.pack_dft_table / audio.pack_basis (audio.MelExtractor holds them)."""
+    if not wav.is_cuda:
+        raise cb.CvftError("libcvft ops need ROCm device tensors; there is no CPU fallback")
+    wav = _c(wav.float())
+    B, Lmax = wav.shape
+    ln = torch.tensor([int(v) for v in lengths], dtype=torch.int32).to(wav.device)
+    out = torch.empty((B, Tmax, 80) if channel_last else (B, 80, Tmax), dtype=torch.float32, device=wav.device)
+    check(lib().cvft_melspec(B, Lmax, Lmax, ptr(wav), ptr(ln), ptr(dft_tab), ptr(basis_tab), nchunks, Tmax,
+                             1 if channel_last else 0, pad_value, ptr(out), stream()), "cvft_melspec")
+    return out

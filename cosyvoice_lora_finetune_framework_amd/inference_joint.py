@@ -6,6 +6,7 @@ without the text front-end.
         --text-tokens 12,873,44,9 --out mel.npy [--speed 0.9] [--seed 0] [--dtype bf16]
         [--top-p 0.8 --top-k 25 --win-size 10 --tau-r 0.1] [--llm-config '{...}' --flow-config '{...}'] [--noise z.npy]
         [--hift hift.pt --wav out.wav [--hift-dtype fp32] [--hift-seed 0]]
+        [--prompt-wav p.wav --prompt-tokens 5,9,.. --prompt-text-tokens 3,4,.. --embedding e.npy]
 
 ``--llm`` / ``--flow`` are the merged state_dicts ``merge_joint_weights.py`` writes; ``--text-tokens`` is a comma-separated
 id list or a ``.npy`` file of ids.  The mel is de-normalised with MEL_MEAN / MEL_STD and written as [80, T] float32.
@@ -15,6 +16,9 @@ of other dimensions than CosyVoice-300M; ``--noise`` pins the Flow's initial noi
 ``--hift`` is the HiFT generator's state_dict (``hift.pt``); with it the mel also goes through ``hift.HiFTGenerator`` and
 ``--wav`` is written as 16-bit PCM at 22 050 Hz.  ``--hift-dtype`` is the vocoder's weight dtype (fp32 by default),
 ``--hift-seed`` pins its source's random phase and noise.  Without ``--hift`` only the mel is written.
+``--prompt-wav`` (16-bit PCM at 22 050 Hz) is turned into the Flow's prompt mel on the GPU (``audio.MelExtractor``);
+``--prompt-tokens`` / ``--prompt-text-tokens`` are the prompt's speech and text token ids (they come from the reference's
+tokenizers, which are not rebuilt here) and ``--embedding`` its speaker embedding.  Without them the prompt is empty.
 """
 from __future__ import annotations
 
@@ -35,20 +39,32 @@ from .config import MEL_MEAN, MEL_STD
 
 @torch.no_grad()
 def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] = None,
-               noise: Optional[torch.Tensor] = None) -> Tuple[List[int], torch.Tensor]:
+               noise: Optional[torch.Tensor] = None, *, prompt_wav: Optional[torch.Tensor] = None,
+               prompt_speech_token=None, prompt_text=None, embedding: Optional[torch.Tensor] = None
+               ) -> Tuple[List[int], torch.Tensor]:
     """-> (speech tokens, de-normalised mel (1, 80, T) fp32).  `seed` pins the LLM's sampler, `noise` the Flow's
-    initial z."""
+    initial z.  Zero-shot prompting: `prompt_wav` (samples at 22 050 Hz) becomes the Flow's `prompt_feat` -- its log-mel
+    (audio.MelExtractor), normalised with MEL_MEAN / MEL_STD as the reference's patched flow inference does for a
+    non-empty prompt --, `prompt_speech_token` goes to both models, `prompt_text` to the LLM, `embedding` (1, 192) to
+    both.  With none of them the prompt is empty and the embedding zero."""
     dev = llm.llm_decoder.weight.device
     text = torch.as_tensor(text_tokens, dtype=torch.long).reshape(1, -1).to(dev)
     z = torch.zeros(1, 0, dtype=torch.long, device=dev)
     zero = torch.tensor([0])
-    emb = torch.zeros(1, 192, device=dev)
-    tokens = list(llm.inference(text, torch.tensor([text.shape[1]]), z, zero, z, zero, emb, seed=seed))
+    ids = lambda v: z if v is None else torch.as_tensor(v, dtype=torch.long).reshape(1, -1).to(dev)   # noqa: E731
+    p_tok, p_text = ids(prompt_speech_token), ids(prompt_text)
+    emb = torch.zeros(1, 192, device=dev) if embedding is None else embedding.float().reshape(1, -1).to(dev)
+    if prompt_wav is None:
+        p_feat = torch.zeros(1, 0, 80, device=dev)
+    else:
+        from .audio import extractor
+        p_feat = (extractor(dev)(prompt_wav.float().reshape(1, -1).to(dev), channel_last=True) - MEL_MEAN) / MEL_STD
+    n = lambda t: torch.tensor([t.shape[1]])                                                           # noqa: E731
+    tokens = list(llm.inference(text, n(text), p_text, n(p_text), p_tok, n(p_tok), emb, seed=seed))
     if not tokens:
         raise RuntimeError("the LLM produced no speech tokens")
     tok = torch.tensor([tokens], dtype=torch.long, device=dev)
-    mel, _ = flow.inference(tok, torch.tensor([len(tokens)]), z, zero, torch.zeros(1, 0, 80, device=dev), zero,
-                            torch.zeros(1, 192, device=dev), noise=noise)
+    mel, _ = flow.inference(tok, torch.tensor([len(tokens)]), p_tok, n(p_tok), p_feat, n(p_feat), emb, noise=noise)
     mel = mel * MEL_STD + MEL_MEAN
     if speed != 1.0:
         mel = F.interpolate(mel, size=int(mel.shape[2] / speed), mode='linear')
@@ -100,6 +116,10 @@ def main(argv=None):
     ap.add_argument('--llm-config', default='{}', help='JSON keyword arguments of build_llm_model')
     ap.add_argument('--flow-config', default='{}', help='JSON keyword arguments of build_flow_model')
     ap.add_argument('--noise', default=None, help='.npy of the Flow\'s initial noise [1, 80, T]')
+    ap.add_argument('--prompt-wav', default=None, help='zero-shot prompt: 16-bit PCM at 22 050 Hz (its mel conditions the Flow)')
+    ap.add_argument('--prompt-tokens', default=None, help='the prompt\'s speech token ids (comma-separated or .npy)')
+    ap.add_argument('--prompt-text-tokens', default=None, help='the prompt\'s text token ids (comma-separated or .npy)')
+    ap.add_argument('--embedding', default=None, help='.npy of the speaker embedding (192 floats); default zero')
     ap.add_argument('--hift', default=None, help='HiFT generator state_dict (hift.pt): also vocode the mel')
     ap.add_argument('--wav', default='out.wav', help='with --hift: the waveform, 16-bit PCM at 22 050 Hz')
     ap.add_argument('--hift-dtype', choices=('fp32', 'bf16'), default='fp32')
@@ -115,7 +135,19 @@ def main(argv=None):
     llm, flow = llm.to(dev).eval(), flow.to(dev).eval()
     llm.sampling = functools.partial(U.ras_sampling, top_p=a.top_p, top_k=a.top_k, win_size=a.win_size, tau_r=a.tau_r)
     noise = torch.from_numpy(np.load(a.noise)).float().to(dev) if a.noise else None
-    tokens, mel = synthesize(llm, flow, _text_tokens(a.text_tokens), a.speed, a.seed, noise=noise)
+    prompt = {}
+    if a.prompt_wav:
+        from .audio import check_rate, load_wav
+        wav, rate = load_wav(a.prompt_wav)
+        check_rate(rate)
+        prompt['prompt_wav'] = wav
+    if a.prompt_tokens:
+        prompt['prompt_speech_token'] = _text_tokens(a.prompt_tokens)
+    if a.prompt_text_tokens:
+        prompt['prompt_text'] = _text_tokens(a.prompt_text_tokens)
+    if a.embedding:
+        prompt['embedding'] = torch.from_numpy(np.load(a.embedding)).float()
+    tokens, mel = synthesize(llm, flow, _text_tokens(a.text_tokens), a.speed, a.seed, noise=noise, **prompt)
     np.save(a.out, mel[0].cpu().numpy().astype(np.float32))
     print(f"{len(tokens)} speech tokens -> mel {tuple(mel.shape[1:])} -> {a.out}")
     if a.hift:

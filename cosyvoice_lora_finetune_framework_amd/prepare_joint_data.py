@@ -1,0 +1,147 @@
+"""Wavs + precomputed tokens -> the parquet shards ``dataset.FlowFinetuneDataset`` reads: the mel leg and the writer of
+the reference's ``prepare_joint_data.py``.
+
+    python -m cosyvoice_lora_finetune_framework_amd.prepare_joint_data --manifest m.jsonl --output-dir D \\
+        [--samples-per-file 100] [--batch 16]
+
+Each manifest line is a JSON object with ``utt``, ``wav`` (16-bit PCM at 22 050 Hz; a relative path is taken from the
+manifest's directory), ``text``, ``text_token``, ``speech_token`` (id lists) and ``utt_embedding`` (192 floats).  The
+reference computes those three with its text tokenizer and two ONNX models (speech tokenizer, speaker encoder), which
+this project does not rebuild, so they come precomputed; what is computed here is ``speech_feat``,
+the [T, 80] log-mel the Flow is trained on, on the GPU (``audio.MelExtractor``) in length-sorted ragged batches.
+
+Like the reference (prepare_joint_data.py:252-256) utterances shorter than 0.5 s or longer than 30 s are dropped.
+Output: ``data_%06d.parquet`` with the reference's columns -- utt, text, text_token, speech_token, speech_feat
+(flattened), speech_feat_shape, utt_embedding, spk_embedding -- and ``data.list`` naming the shards.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import wave
+from typing import Any, Dict, List, Tuple
+
+import torch
+
+from . import audio as A
+
+MIN_SECONDS, MAX_SECONDS = 0.5, 30.0
+REQUIRED = ("utt", "wav", "text", "text_token", "speech_token", "utt_embedding")
+COLUMNS = ("utt", "text", "text_token", "speech_token", "speech_feat", "speech_feat_shape", "utt_embedding", "spk_embedding")
+
+
+def read_manifest(path: str) -> List[Dict[str, Any]]:
+    """JSON lines -> entries with every REQUIRED key; `wav` resolved against the manifest's directory."""
+    base = os.path.dirname(os.path.abspath(path))
+    out = []
+    with open(path, "r", encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            line = line.strip()
+            if not line:
+                continue
+            e = json.loads(line)
+            missing = [k for k in REQUIRED if k not in e]
+            if missing:
+                raise ValueError(f"{path}:{no}: missing {', '.join(missing)}")
+            if not e["text_token"] or not e["speech_token"]:
+                raise ValueError(f"{path}:{no}: {e['utt']}: empty token list")
+            e = dict(e)
+            if not os.path.isabs(e["wav"]):
+                e["wav"] = os.path.join(base, e["wav"])
+            out.append(e)
+    return out
+
+
+def keep_duration(n_samples: int, rate: int) -> bool:
+    """the reference's duration filter: 0.5 s <= duration <= 30 s."""
+    return MIN_SECONDS <= n_samples / rate <= MAX_SECONDS
+
+
+def wav_info(path: str) -> Tuple[int, int]:
+    """(samples per channel, rate) from the file's header."""
+    with wave.open(path, "rb") as f:
+        return f.getnframes(), f.getframerate()
+
+
+def filter_entries(entries: List[Dict[str, Any]], verbose: bool = True) -> List[Dict[str, Any]]:
+    kept = []
+    for e in entries:
+        n, rate = wav_info(e["wav"])
+        if keep_duration(n, rate):
+            kept.append(e)
+        elif verbose:
+            print(f"  skip {e['utt']}: {n / rate:.1f} s outside [{MIN_SECONDS}, {MAX_SECONDS}]")
+    return kept
+
+
+def extract_feats(entries: List[Dict[str, Any]], device, batch: int = 16) -> List[torch.Tensor]:
+    """speech_feat [T, 80] (CPU fp32) per entry, in the entries' order; batches are formed after sorting by length."""
+    ext = A.extractor(device)
+    wavs = []
+    for e in entries:
+        w, rate = A.load_wav(e["wav"])
+        A.check_rate(rate)
+        wavs.append(w)
+    order = sorted(range(len(wavs)), key=lambda i: wavs[i].shape[0])
+    feats: List[Any] = [None] * len(wavs)
+    for i0 in range(0, len(order), batch):
+        idx = order[i0:i0 + batch]
+        lens = [wavs[i].shape[0] for i in idx]
+        pad = torch.zeros(len(idx), max(lens))
+        for r, i in enumerate(idx):
+            pad[r, :lens[r]] = wavs[i]
+        mel = ext(pad.to(device), lens, channel_last=True).cpu()
+        for r, i in enumerate(idx):
+            feats[i] = mel[r, :A.n_frames(lens[r])].contiguous()
+    return feats
+
+
+def make_row(e: Dict[str, Any], feat: torch.Tensor) -> Dict[str, Any]:
+    emb = [float(v) for v in e["utt_embedding"]]
+    return {"utt": e["utt"], "text": e["text"], "text_token": [int(v) for v in e["text_token"]],
+            "speech_token": [int(v) for v in e["speech_token"]], "speech_feat": feat.reshape(-1).tolist(),
+            "speech_feat_shape": [int(feat.shape[0]), int(feat.shape[1])], "utt_embedding": emb, "spk_embedding": emb}
+
+
+def write_shard(rows: List[Dict[str, Any]], output_dir: str, index: int) -> str:
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    path = os.path.join(output_dir, f"data_{index:06d}.parquet")
+    pq.write_table(pa.Table.from_pydict({c: [r[c] for r in rows] for c in COLUMNS}), path)
+    return path
+
+
+def prepare(manifest: str, output_dir: str, samples_per_file: int = 100, batch: int = 16, device="cuda",
+            verbose: bool = True) -> List[str]:
+    """-> the shard paths written (also listed in output_dir/data.list)."""
+    os.makedirs(output_dir, exist_ok=True)
+    entries = filter_entries(read_manifest(manifest), verbose)
+    if not entries:
+        raise RuntimeError(f"{manifest}: no utterance left after the duration filter")
+    shards = []
+    for i0 in range(0, len(entries), samples_per_file):
+        part = entries[i0:i0 + samples_per_file]
+        rows = [make_row(e, f) for e, f in zip(part, extract_feats(part, device, batch))]
+        shards.append(write_shard(rows, output_dir, len(shards)))
+        if verbose:
+            print(f"  wrote {shards[-1]} ({len(rows)} utterances)")
+    with open(os.path.join(output_dir, "data.list"), "w") as f:
+        for p in shards:
+            f.write(p + "\n")
+    return shards
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--manifest", required=True, help="JSON lines: utt, wav, text, text_token, speech_token, utt_embedding")
+    ap.add_argument("--output-dir", required=True)
+    ap.add_argument("--samples-per-file", type=int, default=100)
+    ap.add_argument("--batch", type=int, default=16)
+    a = ap.parse_args(argv)
+    shards = prepare(a.manifest, a.output_dir, a.samples_per_file, a.batch)
+    print(f"{len(shards)} shard(s) -> {os.path.join(a.output_dir, 'data.list')}")
+
+
+if __name__ == "__main__":
+    main()

@@ -607,6 +607,25 @@ int cvft_hift_source(int B, int H, int L, int rep, const float* f0, const float*
 int cvft_hift_stft(int B, int L, const float* s, float* out, void* stream);
 int cvft_hift_istft(int B, int F, const float* x, int ldx, float limit, float* wav, float* mag_out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Mel front-end (matcha/utils/audio.py mel_spectrogram at the CosyVoice-300M setting: n_fft 1024, hop 256, window 1024,
+ * 80 bands, 22 050 Hz, center=False; melspec.hip).  One launch, no atomics, bit-identical run to run and row by row.
+ *
+ * cvft_melspec: wav [B][ldw] fp32 (row b holds len[b] <= Lmax samples; len == NULL: every row holds Lmax) -> log-mel
+ *   out [B][80][Tmax] (channel_last == 0) or [B][Tmax][80] (channel_last != 0).  Row b has T_b = min(len[b] / 256, Tmax)
+ *   frames; frames t >= T_b are set to pad_value (a row with len[b] < 385 has none: the reflect padding of 384 samples
+ *   per side needs 385).  Frame t is padded samples [256 t, 256 t + 1024), padded index p -> sample s = p - 384,
+ *   s < 0: -s, s >= len: 2 (len - 1) - s; times the periodic Hann window; real DFT; mag = sqrt(re^2 + im^2 + 1e-9);
+ *   mel = basis . mag; out = log(max(mel, 1e-5)).
+ *   dft_tab: nchunks * 64 * 2 * 64 * 4 floats, [chunk c][step s][cos | sin][lane l][e] = hann[n] * cos | sin(2 pi n k / 1024)
+ *   with k = 16 c + (l & 15), n = 256 (s >> 4) + 64 (l >> 4) + 4 (s & 15) + e.  basis_tab: nchunks * 5 * 64 * 4 floats,
+ *   [c][band tile m][lane l][i] = basis[16 m + (l & 15)][16 c + 4 (l >> 4) + i].  Both are zero where the bin or band does
+ *   not exist; nchunks = ceil((last bin with filterbank weight + 1) / 16) <= 33.  Both 16-byte aligned.
+ *   (audio.py: pack_dft_table / pack_basis build them.)
+ * ------------------------------------------------------------------------------- */
+int cvft_melspec(int B, int Lmax, int ldw, const float* wav, const int* len, const float* dft_tab, const float* basis_tab,
+                 int nchunks, int Tmax, int channel_last, float pad_value, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
