@@ -31,9 +31,13 @@ struct RankProb {             // one gradient product: slabs of  Rk^T Wd  ([r, C
     size_t part_stride; int rows_per_block;
 };
 struct RankPair { RankProb p[4]; };      // up to four problems per launch (blockIdx.z)
+// DROP form: the wide operand is drop_site(Wd) = keep(seed, site, m * Cn + c) * Wd / (1 - p), the lora_dropout input of dA = V^T drop(x),
+// re-derived on the chunk while it sits in LDS (the mask is a pure function of the element index, common.h) instead of read from a
+// copy the forward pass wrote.  Needs ldw == Cn (the mask index space is the contiguous [M][Cn] tensor).
+struct RankMask { const long long* seed; unsigned site; float p; };
 
-template <int RB>
-__device__ __forceinline__ void lora_rank_body(int M, const RankProb& pr) {
+template <int RB, bool DROP = false>
+__device__ __forceinline__ void lora_rank_body(int M, const RankProb& pr, const RankMask& mk = RankMask{nullptr, 0u, 0.f}) {
     const int Cn = pr.Cn, ldw = pr.ldw, ldr = pr.ldr, ldo = pr.ldo, transpose_out = pr.transpose_out;
     const int rows_per_block = pr.rows_per_block;
     const bf16_t* __restrict__ Wd = pr.Wd;
@@ -77,6 +81,40 @@ __device__ __forceinline__ void lora_rank_body(int M, const RankProb& pr) {
         w_row[i] = r;
         w_chk[i] = min((c0 >> 3) + ((lane & 7) ^ f), nchk - 1);
     }
+    // DROP: each lane masks the four 16-byte slots it requested itself (row m, global chunk w_chk[i]): two draws of four keep flags,
+    // bf16(x * 1 / (1 - p)) for kept elements, +0 for dropped ones -- bit for bit what the forward rank-side kernel would have
+    // written as drop(x) (skinny.hip).  The buffer is the wave's own: LDS operations of one wave complete in order, no barrier.
+    unsigned long long mkey = 0;
+    unsigned mthr = 0;
+    float inv_keep = 1.f;
+    if constexpr (DROP) {
+        mkey = cvft_drop_key(mk.seed, mk.site);
+        mthr = cvft_drop_thr(mk.p);
+        inv_keep = 1.f / (1.f - mk.p);
+    }
+    auto mask_chunk = [&](int chunk, int buf) __attribute__((always_inline)) {
+        const int m0 = mb + chunk * 32;
+        uint4 v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const uint4*>(my + buf * BUF + i * 1024 + lane * 16);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = min(m0 + w_row[i], me - 1);
+            const unsigned long long g = ((unsigned long long)m * Cn + (unsigned long long)w_chk[i] * 8) >> 2;
+            bool k0[4], k1[4];
+            cvft_keep4(mkey, g, mthr, k0);
+            cvft_keep4(mkey, g + 1, mthr, k1);
+            v[i].x &= (k0[0] ? 0x0000ffffu : 0u) | (k0[1] ? 0xffff0000u : 0u);
+            v[i].y &= (k0[2] ? 0x0000ffffu : 0u) | (k0[3] ? 0xffff0000u : 0u);
+            v[i].z &= (k1[0] ? 0x0000ffffu : 0u) | (k1[1] ? 0xffff0000u : 0u);
+            v[i].w &= (k1[2] ? 0x0000ffffu : 0u) | (k1[3] ? 0xffff0000u : 0u);
+            const bf16x8 vm = *reinterpret_cast<const bf16x8*>(&v[i]);
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (bf16_t)((float)vm[e] * inv_keep);
+            *reinterpret_cast<bf16x8*>(my + buf * BUF + i * 1024 + lane * 16) = o;
+        }
+    };
     auto issue = [&](int chunk, int buf) __attribute__((always_inline)) {
         const int m0 = mb + chunk * 32;
 #pragma unroll
@@ -135,6 +173,7 @@ __device__ __forceinline__ void lora_rank_body(int M, const RankProb& pr) {
             issue(c + 1, buf ^ 1);
             load_rk(c + 1);
         }
+        if constexpr (DROP) mask_chunk(c, buf);                // (behind the next chunk's loads: they fly while the VALU masks this one)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const unsigned char* bb = my + buf * BUF;
         bf16x8 a[RB], b[4];
@@ -200,6 +239,15 @@ __global__ void __launch_bounds__(256) lora_rank_mfma_kernel(int M, RankPair pro
     lora_rank_body<RB>(M, prob_pair.p[blockIdx.z]);
 }
 
+// Masked twin: per problem a mask site, or CVFT_RANK_UNMASKED for a plain product (the dB = dY^T U that shares the launch).
+struct RankPairMasked { RankProb p[4]; RankMask m[4]; };
+template <int RB>
+__global__ void __launch_bounds__(256) lora_rank_mfma_masked_kernel(int M, RankPairMasked pm) {
+    const RankMask& mk = pm.m[blockIdx.z];
+    if (mk.site == CVFT_RANK_UNMASKED) lora_rank_body<RB, false>(M, pm.p[blockIdx.z]);
+    else lora_rank_body<RB, true>(M, pm.p[blockIdx.z], mk);
+}
+
 // Batch form: the problems of MANY layers (each with its own row count), one per blockIdx.z, passed by value in the
 // kernel arguments (no device-side table: nothing to upload, so the launch is hipGraph-capturable as is).
 // A backward pass defers the small adapter-gradient products to its end (nothing downstream reads them) and issues
@@ -216,6 +264,22 @@ __global__ void __launch_bounds__(256) lora_rank_mfma_batch_kernel(RankBatch bat
     pr.ldo = pr.transpose_out ? RB * 16 : pr.Cn;
     pr.part_stride = (size_t)(RB * 16) * pr.Cn;
     lora_rank_body<RB>(e.M, pr);
+}
+
+struct RankProbMM { RankProbM e; RankMask m; };
+#define CVFT_RANK_BATCH_MASKED 48
+struct RankBatchMasked { RankProbMM p[CVFT_RANK_BATCH_MASKED]; };   // 48 x 64 B = 3 KB
+template <int RB>
+__global__ void __launch_bounds__(256) lora_rank_mfma_batch_masked_kernel(RankBatchMasked batch) {
+    const RankProbM& e = batch.p[blockIdx.z].e;
+    const RankMask& mk = batch.p[blockIdx.z].m;
+    RankProb pr;
+    pr.Cn = e.Cn; pr.Wd = e.Wd; pr.ldw = e.ldw; pr.Rk = e.Rk; pr.ldr = e.ldr; pr.out = e.out;
+    pr.transpose_out = e.transpose_out; pr.rows_per_block = e.rows_per_block;
+    pr.ldo = pr.transpose_out ? RB * 16 : pr.Cn;
+    pr.part_stride = (size_t)(RB * 16) * pr.Cn;
+    if (mk.site == CVFT_RANK_UNMASKED) lora_rank_body<RB, false>(e.M, pr);
+    else lora_rank_body<RB, true>(e.M, pr, mk);
 }
 
 static bool rank_ok(int Cn, int r, const void* Wd, int ldw, const void* Rk, int ldr, const float* part, int rows_per_block) {
@@ -250,6 +314,31 @@ static void rank_launch(int M, int r, const RankPair& pp, int nprob, hipStream_t
     } while (0)
     if (r == 16) RM_LAUNCH(1); else if (r == 32) RM_LAUNCH(2); else if (r == 48) RM_LAUNCH(3); else RM_LAUNCH(4);
 #undef RM_LAUNCH
+}
+
+static bool rank_mask_ok(unsigned site, float p, const int64_t* seed, int Cn, int ldw) {
+    return site == CVFT_RANK_UNMASKED || (seed && p > 0.f && cvft_drop_rate_ok(p) && ldw == Cn);
+}
+static void rank_launch_masked(int M, int r, const RankPairMasked& pm, int nprob, hipStream_t st) {
+    int gx = 0, gy = 0;
+    for (int i = 0; i < nprob; ++i) {
+        gx = max(gx, pm.p[i].rows_per_block % 128 == 0 ? (pm.p[i].Cn + 63) / 64 : (pm.p[i].Cn + 255) / 256);
+        gy = max(gy, (M + pm.p[i].rows_per_block - 1) / pm.p[i].rows_per_block);
+    }
+    dim3 grid(gx, gy, nprob);
+    const size_t sm = (size_t)4 * 2 * (32 * 128 + 32 * r * 2);
+#define RMM_LAUNCH(RBv)                                                                                                  \
+    do {                                                                                                                 \
+        auto kern = lora_rank_mfma_masked_kernel<RBv>;                                                                   \
+        static bool attr_set = false;                                                                                    \
+        if (sm > 48 * 1024 && !attr_set) {                                                                               \
+            attr_set = true;                                                                                             \
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
+        }                                                                                                                \
+        hipLaunchKernelGGL(kern, grid, dim3(256), sm, st, M, pm);                                                        \
+    } while (0)
+    if (r == 16) RMM_LAUNCH(1); else if (r == 32) RMM_LAUNCH(2); else if (r == 48) RMM_LAUNCH(3); else RMM_LAUNCH(4);
+#undef RMM_LAUNCH
 }
 
 // Slab mode only (part_stride = r * Cn): returns 1 when the operands are not eligible.
@@ -337,5 +426,92 @@ extern "C" int cvft_lora_rank_partial_batch(int r, int n, const cvft_rank_prob_m
 #undef RMB_LAUNCH
     }
     CVFT_LAUNCH_CHECK("cvft_lora_rank_partial_batch");
+    return 0;
+}
+
+// ---- masked twins: the wide operand of a problem with site != CVFT_RANK_UNMASKED is drop_site(Wd), the mask re-derived in LDS ----
+// partA[s] = V^T drop_site(X) (X contiguous rows of K: ldx == K), partB[s] = dY^T U unmasked, one launch.
+extern "C" int cvft_lora_rank_partial_pair_masked(int M, int r, int K, const void* X, int ldx, const void* V, int ldv, float* partA,
+                                                  int rpbA, int N, const void* dY, int ldy, const void* U, int ldu, float* partB,
+                                                  int rpbB, const int64_t* seed, unsigned site, float p, void* stream) {
+    CVFT_CHECK_ARG(M > 0 && X && V && partA && dY && U && partB, "cvft_lora_rank_partial_pair_masked: bad args");
+    CVFT_CHECK_ARG(rank_ok(K, r, X, ldx, V, ldv, partA, rpbA) && rank_ok(N, r, dY, ldy, U, ldu, partB, rpbB),
+                   "cvft_lora_rank_partial_pair_masked: bf16 operands must be 16-byte aligned, widths %% 8 == 0, r in {16,32,48,64}, rows_per_block %% 32 == 0");
+    CVFT_CHECK_ARG(rank_mask_ok(site, p, seed, K, ldx),
+                   "cvft_lora_rank_partial_pair_masked: bad dropout args (seed, 2^-16 <= p <= 1 - 2^-16, ldx == K)");
+    RankPairMasked pm;
+    pm.p[0] = make_prob(K, r, X, ldx, V, ldv, partA, 0, rpbA);
+    pm.p[1] = make_prob(N, r, dY, ldy, U, ldu, partB, 1, rpbB);
+    pm.p[2] = pm.p[3] = pm.p[0];
+    pm.m[0] = RankMask{(const long long*)seed, site, p};
+    pm.m[1] = RankMask{nullptr, CVFT_RANK_UNMASKED, 0.f};
+    pm.m[2] = pm.m[3] = pm.m[1];
+    rank_launch_masked(M, r, pm, 2, (hipStream_t)stream);
+    CVFT_LAUNCH_CHECK("cvft_lora_rank_partial_pair_masked");
+    return 0;
+}
+
+extern "C" int cvft_lora_rank_partial_multi_masked(int M, int r, int n, const cvft_rank_prob_masked* probs, void* stream) {
+    CVFT_CHECK_ARG(M > 0 && n >= 1 && n <= 4 && probs, "cvft_lora_rank_partial_multi_masked: 1 <= n <= 4");
+    RankPairMasked pm;
+    for (int i = 0; i < n; ++i) {
+        const cvft_rank_prob& q = probs[i].prob;
+        CVFT_CHECK_ARG(q.Wd && q.Rk && q.part && rank_ok(q.C, r, q.Wd, q.ldw, q.Rk, q.ldr, q.part, q.rows_per_block),
+                       "cvft_lora_rank_partial_multi_masked: problem %d: bf16 operands 16-byte aligned, widths %% 8 == 0, r in {16,32,48,64}", i);
+        CVFT_CHECK_ARG(rank_mask_ok(probs[i].site, probs[i].p, probs[i].seed, q.C, q.ldw),
+                       "cvft_lora_rank_partial_multi_masked: problem %d: bad dropout args (seed, 2^-16 <= p <= 1 - 2^-16, ldw == C)", i);
+        pm.p[i] = make_prob(q.C, r, q.Wd, q.ldw, q.Rk, q.ldr, q.part, q.transpose_out, q.rows_per_block);
+        pm.m[i] = RankMask{(const long long*)probs[i].seed, probs[i].site, probs[i].p};
+    }
+    for (int i = n; i < 4; ++i) { pm.p[i] = pm.p[0]; pm.m[i] = pm.m[0]; }
+    rank_launch_masked(M, r, pm, n, (hipStream_t)stream);
+    CVFT_LAUNCH_CHECK("cvft_lora_rank_partial_multi_masked");
+    return 0;
+}
+
+// n slab products of rank r, each with its own row count and mask site, in ceil(n / 48) launches.
+extern "C" int cvft_lora_rank_partial_batch_masked(int r, int n, const cvft_rank_prob_m_masked* probs, void* stream) {
+    CVFT_CHECK_ARG((r == 16 || r == 32 || r == 48 || r == 64) && n >= 1 && probs, "cvft_lora_rank_partial_batch_masked: r in {16,32,48,64}, n >= 1");
+    for (int i = 0; i < n; ++i) {
+        const cvft_rank_prob_m& q = probs[i].prob;
+        CVFT_CHECK_ARG(q.M > 0 && q.Wd && q.Rk && q.part && rank_ok(q.C, r, q.Wd, q.ldw, q.Rk, q.ldr, q.part, q.rows_per_block),
+                       "cvft_lora_rank_partial_batch_masked: problem %d: bf16 operands 16-byte aligned, widths %% 8 == 0, rows_per_block %% 32 == 0", i);
+        CVFT_CHECK_ARG(rank_mask_ok(probs[i].site, probs[i].p, probs[i].seed, q.C, q.ldw),
+                       "cvft_lora_rank_partial_batch_masked: problem %d: bad dropout args (seed, 2^-16 <= p <= 1 - 2^-16, ldw == C)", i);
+    }
+    const size_t sm = (size_t)4 * 2 * (32 * 128 + 32 * r * 2);
+    hipStream_t st = (hipStream_t)stream;
+    for (int i0 = 0; i0 < n; i0 += CVFT_RANK_BATCH_MASKED) {
+        const int nb = min(CVFT_RANK_BATCH_MASKED, n - i0);
+        RankBatchMasked bt;
+        int gx = 1, gy = 1;
+        for (int i = 0; i < CVFT_RANK_BATCH_MASKED; ++i) {
+            const cvft_rank_prob_m_masked& qm = probs[i0 + (i < nb ? i : 0)];
+            const cvft_rank_prob_m& q = qm.prob;
+            RankProbM& e = bt.p[i].e;
+            e.Wd = (const bf16_t*)q.Wd; e.Rk = (const bf16_t*)q.Rk; e.out = q.part; e.M = q.M; e.Cn = q.C; e.ldw = q.ldw; e.ldr = q.ldr;
+            e.rows_per_block = q.rows_per_block; e.transpose_out = q.transpose_out;
+            bt.p[i].m = RankMask{(const long long*)qm.seed, qm.site, qm.p};
+            if (i < nb) {
+                gx = max(gx, q.rows_per_block % 128 == 0 ? (q.C + 63) / 64 : (q.C + 255) / 256);
+                gy = max(gy, (q.M + q.rows_per_block - 1) / q.rows_per_block);
+            }
+        }
+        CVFT_CHECK_ARG(gy <= 65535, "cvft_lora_rank_partial_batch_masked: too many row blocks");
+        dim3 grid(gx, gy, nb);
+#define RMBM_LAUNCH(RBv)                                                                                                 \
+    do {                                                                                                                 \
+        auto kern = lora_rank_mfma_batch_masked_kernel<RBv>;                                                             \
+        static bool attr_set = false;                                                                                    \
+        if (sm > 48 * 1024 && !attr_set) {                                                                               \
+            attr_set = true;                                                                                             \
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
+        }                                                                                                                \
+        hipLaunchKernelGGL(kern, grid, dim3(256), sm, st, bt);                                                           \
+    } while (0)
+        if (r == 16) RMBM_LAUNCH(1); else if (r == 32) RMBM_LAUNCH(2); else if (r == 48) RMBM_LAUNCH(3); else RMBM_LAUNCH(4);
+#undef RMBM_LAUNCH
+    }
+    CVFT_LAUNCH_CHECK("cvft_lora_rank_partial_batch_masked");
     return 0;
 }

@@ -35,6 +35,19 @@ class RankProbM(C.Structure):
                 ("part", C.c_void_p), ("transpose_out", C.c_int), ("rows_per_block", C.c_int)]
 
 
+RANK_UNMASKED = 0xffffffff   # CVFT_RANK_UNMASKED (include/cvft.h)
+
+
+class RankProbMasked(C.Structure):
+    """mirror of cvft_rank_prob_masked (include/cvft.h)"""
+    _fields_ = [("prob", RankProb), ("seed", C.c_void_p), ("site", C.c_uint), ("p", C.c_float)]
+
+
+class RankProbMMasked(C.Structure):
+    """mirror of cvft_rank_prob_m_masked (include/cvft.h)"""
+    _fields_ = [("prob", RankProbM), ("seed", C.c_void_p), ("site", C.c_uint), ("p", C.c_float)]
+
+
 class BlockTailArgs(C.Structure):
     """mirror of cvft_block_tail_args (include/cvft.h)"""
     _fields_ = [("M", C.c_int), ("o", C.c_void_p), ("ldo", C.c_int), ("DI", C.c_int), ("x0", C.c_void_p),
@@ -121,6 +134,9 @@ SIGNATURES = {
     "cvft_lora_rank_partial_pair": [_i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _i, _p, _i, _p],
     "cvft_lora_rank_partial_multi": [_i, _i, _i, _p, _p],
     "cvft_lora_rank_partial_batch": [_i, _i, _p, _p],
+    "cvft_lora_rank_partial_pair_masked": [_i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _i, _p, _i, _p, C.c_uint, _f, _p],
+    "cvft_lora_rank_partial_multi_masked": [_i, _i, _i, _p, _p],
+    "cvft_lora_rank_partial_batch_masked": [_i, _i, _p, _p],
     "cvft_debug_glds_stamps": [_p],
     "cvft_debug_stamp": [_p, C.c_int, _p],
     "cvft_debug_mfma_fp8_probe": [_p, _p, _p, _p],

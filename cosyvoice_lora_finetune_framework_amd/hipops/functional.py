@@ -485,10 +485,12 @@ def ln_skinny_dropout(x: torch.Tensor, gamma, beta, eps: float, A: torch.Tensor,
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
     U = torch.empty((M, A.shape[0]), dtype=x.dtype, device=x.device)
     sites = [_next_drop_site() for _ in range(nsites)]
-    outs = [torch.empty_like(x) for _ in sites]
-    for st, t in zip(sites, outs):
-        _DROPPED[st] = t
-    xd = (C.c_void_p * 3)(*([t.data_ptr() for t in outs] + [None] * (3 - len(outs))))
+    xd = None
+    if not rank_mask_fwd_ok(x, 16 if nsites == 3 else A.shape[0]):
+        outs = [torch.empty_like(x) for _ in sites]
+        for st, t in zip(sites, outs):
+            _DROPPED[st] = t
+        xd = (C.c_void_p * 3)(*([t.data_ptr() for t in outs] + [None] * (3 - len(outs))))
     check(lib().cvft_ln_skinny_dropout(M, K, A.shape[0], ptr(x), ptr(gamma), ptr(beta), float(eps), ptr(y), ptr(mean), ptr(rstd),
                                        ptr(A), A.stride(0), float(alpha), ptr(U), U.stride(0), float(p), ptr(_DROPOUT["seed"]),
                                        _sites_arr(sites), xd, stream()), "cvft_ln_skinny_dropout")
@@ -510,8 +512,8 @@ def skinny_dropout(x: torch.Tensor, A: torch.Tensor, alpha: float, p: float, sit
     xd = None
     if len(sites) == 1 and A.shape[0] > 16:
         sites = list(sites) * (A.shape[0] // 16)          # ONE adapter of rank > 16: every rank tile under the same mask
-    if keep_dropped and KEEP_DROPPED:
-        uniq = list(dict.fromkeys(sites))                 # one dropped copy per distinct mask site
+    uniq = list(dict.fromkeys(sites))                     # one dropped copy per distinct mask site
+    if keep_dropped and KEEP_DROPPED and not rank_mask_fwd_ok(x, A.shape[0] // len(uniq)):
         outs = [torch.empty_like(x) for _ in uniq]
         for st, t in zip(uniq, outs):
             _DROPPED[st] = t
@@ -520,6 +522,20 @@ def skinny_dropout(x: torch.Tensor, A: torch.Tensor, alpha: float, p: float, sit
                                     ptr(U), U.stride(0), float(p), ptr(_DROPOUT["seed"]), _sites_arr(sites), xd, stream()),
           "cvft_skinny_dropout")
     return U
+
+
+def rank_mask_fwd_ok(x: torch.Tensor, r: int) -> bool:
+    """Forward side of CVFT_RANK_MASK: no dropped copy is written when the adapter-gradient launch of this backward can re-derive
+    the mask on x itself (masked form of the slab kernels, csrc/lora_grad.hip): bf16 contiguous x, r in {16, 32, 48, 64}, inside
+    an active LoraGradSink.  A backward that then runs without a sink re-derives drop(x) in a pass of its own (dropped_input)."""
+    return (RANK_MASK and LoraGradSink.active is not None and x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0 and x.shape[1] % 8 == 0 and r in (16, 32, 48, 64))
+
+
+def rank_mask_bwd_ok(x: torch.Tensor, r: int) -> bool:
+    """Backward side: x can go to the masked slab launch as it is (the copy's absence from _DROPPED is checked by the caller)."""
+    return (RANK_MASK and x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0
+            and x.shape[1] % 8 == 0 and r in (16, 32, 48, 64))
 
 
 def dropped_input(x: torch.Tensor, p: float, site: int) -> torch.Tensor:
@@ -686,37 +702,60 @@ class LoraGradSink:
         """Batched launches fill the chip by their problem count: long row blocks (fewer, smaller slabs to write and reduce)."""
         return SINK_DEFER_RPB, -(-M // SINK_DEFER_RPB)
 
-    def rank_pair(self, defer: bool, M: int, r: int, K: int, x, V, wsA, rpa: int, N: int, dY, U, wsB, rpb: int):
+    def rank_pair(self, defer: bool, M: int, r: int, K: int, x, V, wsA, rpa: int, N: int, dY, U, wsB, rpb: int, mask=None):
         """slabs of dA = V^T x ([r, K] per row block of rpa rows) and dB = dY^T U ([N, r] per row block of rpb rows): now, or
-        at flush() when `defer`."""
+        at flush() when `defer`.  mask = (p, site): dA = V^T drop_site(x), the mask re-derived inside the launch."""
         if not defer:
+            if mask is not None:
+                check(lib().cvft_lora_rank_partial_pair_masked(M, r, K, ptr(x), x.stride(0), ptr(V), V.stride(0), ptr(wsA), rpa,
+                                                               N, ptr(dY), dY.stride(0), ptr(U), U.stride(0), ptr(wsB), rpb,
+                                                               ptr(_DROPOUT["seed"]), int(mask[1]), float(mask[0]), stream()),
+                      "cvft_lora_rank_partial_pair_masked")
+                return
             check(lib().cvft_lora_rank_partial_pair(M, r, K, ptr(x), x.stride(0), ptr(V), V.stride(0), ptr(wsA), rpa,
                                                     N, ptr(dY), dY.stride(0), ptr(U), U.stride(0), ptr(wsB), rpb, stream()),
                   "cvft_lora_rank_partial_pair")
             return
-        for C, Wd, Rk, ws, tr, rp in ((K, x, V, wsA, 0, rpa), (N, dY, U, wsB, 1, rpb)):
+        for C, Wd, Rk, ws, tr, rp, mk in ((K, x, V, wsA, 0, rpa, mask), (N, dY, U, wsB, 1, rpb, None)):
             assert (C % 8 == 0 and Wd.stride(0) % 8 == 0 and Rk.stride(0) % 8 == 0 and Wd.data_ptr() % 16 == 0 and Rk.data_ptr() % 16 == 0
                     and ws.data_ptr() % 16 == 0 and rp % 32 == 0 and Wd.dtype == Rk.dtype == torch.bfloat16 and Rk.shape[1] == r)
             self.deferred.setdefault(r, []).append((M, C, Wd.data_ptr(), Wd.stride(0), Rk.data_ptr(), Rk.stride(0), ws.data_ptr(), tr, rp,
-                                                    torch.cuda.current_stream().cuda_stream))
+                                                    torch.cuda.current_stream().cuda_stream, LoraGradSink._mask_row(mk, Wd, C)))
         self.keep.append((x, V, dY, U))
         self._note_stream()
         self._deferred_added(r)
 
-    def defer_one(self, M: int, r: int, C_: int, Wd, Rk, ws, transpose_out: int, rpb: int, keep=()):
-        """Postpone ONE slab product (slabs of Rk^T Wd, [r, C] or [C, r] when transpose_out) to flush()."""
+    @staticmethod
+    def _mask_row(mask, Wd, C_: int):
+        """(seed address, site, p) of a masked deferred row, or None"""
+        if mask is None:
+            return None
+        assert Wd.stride(0) == C_
+        return (_DROPOUT["seed"].data_ptr(), int(mask[1]), float(mask[0]))
+
+    def defer_one(self, M: int, r: int, C_: int, Wd, Rk, ws, transpose_out: int, rpb: int, keep=(), mask=None):
+        """Postpone ONE slab product (slabs of Rk^T Wd, [r, C] or [C, r] when transpose_out) to flush().
+        mask = (p, site): the wide operand is drop_site(Wd), re-derived inside the launch."""
         assert (C_ % 8 == 0 and Wd.stride(0) % 8 == 0 and Rk.stride(0) % 8 == 0 and Wd.data_ptr() % 16 == 0 and Rk.data_ptr() % 16 == 0
                 and ws.data_ptr() % 16 == 0 and rpb % 32 == 0 and Wd.dtype == Rk.dtype == torch.bfloat16 and Rk.shape[1] == r)
         self.deferred.setdefault(r, []).append((M, C_, Wd.data_ptr(), Wd.stride(0), Rk.data_ptr(), Rk.stride(0), ws.data_ptr(), transpose_out, rpb,
-                                                torch.cuda.current_stream().cuda_stream))
+                                                torch.cuda.current_stream().cuda_stream, LoraGradSink._mask_row(mask, Wd, C_)))
         self.keep.append((Wd, Rk, ws) + tuple(keep))
         self._note_stream()
         self._deferred_added(r)
 
     @staticmethod
     def _launch_rows(r: int, rows):
+        if any(row[10] is not None for row in rows):          # masked dA products (and the plain dB products that ride along)
+            arr = (cb.RankProbMMasked * len(rows))()
+            for em, (M, Cn, Wd, ldw, Rk, ldr, ws, tr, rp, _, mk) in zip(arr, rows):
+                e = em.prob
+                e.M, e.C, e.Wd, e.ldw, e.Rk, e.ldr, e.part, e.transpose_out, e.rows_per_block = M, Cn, Wd, ldw, Rk, ldr, ws, tr, rp
+                em.seed, em.site, em.p = (None, cb.RANK_UNMASKED, 0.0) if mk is None else mk
+            check(lib().cvft_lora_rank_partial_batch_masked(r, len(rows), arr, stream()), "cvft_lora_rank_partial_batch_masked")
+            return
         arr = (cb.RankProbM * len(rows))()
-        for e, (M, Cn, Wd, ldw, Rk, ldr, ws, tr, rp, _) in zip(arr, rows):
+        for e, (M, Cn, Wd, ldw, Rk, ldr, ws, tr, rp, _, _mk) in zip(arr, rows):
             e.M, e.C, e.Wd, e.ldw, e.Rk, e.ldr, e.part, e.transpose_out, e.rows_per_block = M, Cn, Wd, ldw, Rk, ldr, ws, tr, rp
         check(lib().cvft_lora_rank_partial_batch(r, len(rows), arr, stream()), "cvft_lora_rank_partial_batch")
 
@@ -866,7 +905,8 @@ if _os.environ.get('CVFT_FP8', '0') == '1':
 # the stacked q|k|v adapters' four slab products join the sink's end-of-backward batch launches: 26.27 -> 25.91 ms/step with three
 # chains (same-box A/B; it lost 0.7 ms when the step was one chain)
 STACKED_DROP_DEFER = _os.environ.get('CVFT_STACKED_DROP_DEFER', '1') != '0'
-KEEP_DROPPED = _os.environ.get('CVFT_KEEP_DROPPED', '1') != '0'   # forward writes drop(x) for the backward's dA (no re-derivation launch)
+KEEP_DROPPED = _os.environ.get('CVFT_KEEP_DROPPED', '1') != '0'   # forward writes drop(x) for the backward's dA (no re-derivation launch); in effect where CVFT_RANK_MASK is not
+RANK_MASK = _os.environ.get('CVFT_RANK_MASK', '1') != '0'        # dA = V^T drop(x) with the mask re-derived inside the slab launch: no dropped copies at all (0: exactly the path before it)
 LN_SKINNY = _os.environ.get('CVFT_LN_SKINNY', '1') != '0'    # LayerNorm launch also emits the dropped rank-side product of the adapter it feeds
 XDROP_ON = _os.environ.get('CVFT_XDROP', '1') != '0'        # lora_dropout dgrad: masked rank extension inside the GEMM launch
 SINK_PLAN_BLOCKS = int(_os.environ.get('CVFT_SINK_PLAN_BLOCKS', 768))     # wave stripes per launch; with the stacked slab kernel (four waves per stripe and slab), same box: 512 -> 21.57, 768 -> 21.45 / 21.45, 1024 -> 21.56, 1536 -> 21.61 ms (the kernel before it: 21.70; round 3 had 512 best of 256 / 512 / 1024 for one wave per stripe, round 2 256)
@@ -955,9 +995,10 @@ def _lin_fwd(x, A, B, pack: LinearPack, scale: float, act: Optional[str], residu
     return y, U, z, ops
 
 
-def _lora_param_grads(x, U, V, dz, A_ref, B_ref, ops):
+def _lora_param_grads(x, U, V, dz, A_ref, B_ref, ops, mask=None):
     """dA[r,K] += V^T x,  dB[N,r] += dz^T U  (V = s dz B, U = s x A^T): into the parameters' flat .grad buffers -- through the
-    active LoraGradSink (deterministic slabs + one reduce) when there is one, else fp32 atomics -- or returned."""
+    active LoraGradSink (deterministic slabs + one reduce) when there is one, else fp32 atomics -- or returned.
+    mask = (p, site): dA sees drop_site(x); the matrix-core slab launch re-derives the mask itself, any other path gets a copy."""
     dA = dB = None
     A, B = A_ref, B_ref
     gA, gB = A.grad, B.grad
@@ -969,8 +1010,11 @@ def _lora_param_grads(x, U, V, dz, A_ref, B_ref, ops):
     sink = LoraGradSink.active
     r = V.shape[1]
     vec = 8 if x.dtype == torch.bfloat16 else 4
-    if (sink is not None and direct and r % 16 == 0 and x.shape[1] % vec == 0 and dz.shape[1] % vec == 0
-            and x.data_ptr() % 16 == 0 and dz.data_ptr() % 16 == 0):
+    slabs = (sink is not None and direct and r % 16 == 0 and x.shape[1] % vec == 0 and dz.shape[1] % vec == 0
+             and x.data_ptr() % 16 == 0 and dz.data_ptr() % 16 == 0)
+    if mask is not None and not (slabs and rank_mask_bwd_ok(x, r)):
+        x, mask = dropout_raw(x, mask[0], mask[1]), None
+    if slabs:
         M = x.shape[0]
         # the slab kernels are off the critical path (nothing downstream in backward reads them): launch them
         # on the sink's side stream so they overlap the latency-bound dgrad chain; joined in sink.flush()
@@ -986,7 +1030,7 @@ def _lora_param_grads(x, U, V, dz, A_ref, B_ref, ops):
                 rpa, nsa = LoraGradSink.plan_deferred(M) if defer else LoraGradSink.plan(M, x.shape[1])
                 rpb_, nsb = LoraGradSink.plan_deferred(M) if defer else LoraGradSink.plan(M, dz.shape[1])
                 wsA, wsB = sink.workspace(A, nsa), sink.workspace(B, nsb)
-                sink.rank_pair(defer, M, r, x.shape[1], x, V, wsA, rpa, dz.shape[1], dz, U, wsB, rpb_)
+                sink.rank_pair(defer, M, r, x.shape[1], x, V, wsA, rpa, dz.shape[1], dz, U, wsB, rpb_, mask=mask)
                 sink.add(wsA, gA, A.numel(), nsa)
                 sink.add(wsB, gB, B.numel(), nsb)
             else:
@@ -1043,7 +1087,11 @@ def _lin_bwd(x, U, ops, A_ref, B_ref, pack: LinearPack, scale: float, dz, need_d
                 dx = gemm(dz, pack.Wb, residual=dx_residual)
                 dx = producer_chain(side_dgrad(V, Ac, dx, drop[0], [drop[1]]))
         if need_dAB:
-            dA, dB = _lora_param_grads(dropped_input(x, drop[0], drop[1]), U, V, dz, A_ref, B_ref, ops)
+            xd = _DROPPED.pop(drop[1], None)                  # the forward kernel's copy, else the mask is re-derived on x
+            if xd is not None:
+                dA, dB = _lora_param_grads(xd, U, V, dz, A_ref, B_ref, ops)
+            else:
+                dA, dB = _lora_param_grads(x, U, V, dz, A_ref, B_ref, ops, mask=(drop[0], drop[1]))
         return dx, dA, dB
     if has_lora:
         Ac, At, Bc, Bt = ops
@@ -1255,8 +1303,12 @@ class LinearQKVStackedFn(torch.autograd.Function):
         sink = LoraGradSink.active
         grads = [(a.grad, b.grad) for a, b in ctx.refs]
         direct = all(g is not None and g.dtype == torch.float32 and g.is_contiguous() for pair in grads for g in pair)
-        xds = [dropped_input(x, p, st) for st in sites]                 # the three dropped inputs (written by the forward kernel)
-        if sink is not None and direct and sink.side is None:
+        slabs = sink is not None and direct and sink.side is None
+        # the three dropped inputs: written by the forward kernel, or (no copies, CVFT_RANK_MASK) x itself under its three mask sites
+        masked = slabs and rank_mask_bwd_ok(x, r) and not any(st in _DROPPED for st in sites)
+        xds = [x, x, x] if masked else [dropped_input(x, p, st) for st in sites]
+        masks = [(p, st) if masked else None for st in sites]
+        if slabs:
             defer = STACKED_DROP_DEFER and r == 16 and r3 == 48 and sink.will_defer(x, dY)
             rpa, nsa = LoraGradSink.plan_deferred(M) if defer else LoraGradSink.plan(M, K)
             rpb_, nsb = LoraGradSink.plan_deferred(M) if defer else LoraGradSink.plan(M, 3 * N)
@@ -1264,16 +1316,22 @@ class LinearQKVStackedFn(torch.autograd.Function):
             keep = [sink.workspace(ctx.refs[i][0], nsa) for i in range(3)]
             if defer:                       # the four slab products join the sink's end-of-backward batch launches
                 for i in range(3):
-                    sink.defer_one(M, r, K, xds[i], V[:, i * r:(i + 1) * r], keep[i], 0, rpa, keep=(V,))
+                    sink.defer_one(M, r, K, xds[i], V[:, i * r:(i + 1) * r], keep[i], 0, rpa, keep=(V,), mask=masks[i])
                 sink.defer_one(M, r3, 3 * N, dY, U, wsB, 1, rpb_)
             else:
-                probs = (cb.RankProb * 3)()
+                mprobs = (cb.RankProbMasked * 3)() if masked else None
+                probs = [mp.prob for mp in mprobs] if masked else (cb.RankProb * 3)()
                 for i in range(3):
                     Vi = V[:, i * r:(i + 1) * r]
                     probs[i].C, probs[i].Wd, probs[i].ldw = K, xds[i].data_ptr(), xds[i].stride(0)
                     probs[i].Rk, probs[i].ldr, probs[i].part = Vi.data_ptr(), V.stride(0), keep[i].data_ptr()
                     probs[i].transpose_out, probs[i].rows_per_block = 0, rpa
-                check(lib().cvft_lora_rank_partial_multi(M, r, 3, probs, stream()), "cvft_lora_rank_partial_multi")
+                    if masked:
+                        mprobs[i].seed, mprobs[i].site, mprobs[i].p = _DROPOUT["seed"].data_ptr(), sites[i], p
+                if masked:
+                    check(lib().cvft_lora_rank_partial_multi_masked(M, r, 3, mprobs, stream()), "cvft_lora_rank_partial_multi_masked")
+                else:
+                    check(lib().cvft_lora_rank_partial_multi(M, r, 3, probs, stream()), "cvft_lora_rank_partial_multi")
                 check(lib().cvft_lora_rank_partial(dt(dY), M, 3 * N, r3, ptr(dY), dY.stride(0), ptr(U), U.stride(0), ptr(wsB), 1, rpb_,
                                                    stream()), "cvft_lora_rank_partial")
             for i, (gA, _) in enumerate(grads):

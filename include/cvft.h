@@ -163,6 +163,20 @@ typedef struct {
  * in the kernel arguments so the launches are hipGraph-capturable).  Used by a backward pass that defers the small
  * per-layer adapter-gradient products (autograd of lora.py:71-76) to its end. */
 int cvft_lora_rank_partial_batch(int r, int n, const cvft_rank_prob_m* probs, void* stream);
+/* Masked twins (lora_dropout): the wide operand of a problem is drop_site(Wd) = keep(*seed, site, m * C + c) * Wd / (1 - p), with
+ * the mask re-derived on the operand inside the launch (see "Dropout masks") -- bit for bit the product of the plain entry on
+ * the dropped copy cvft_skinny_dropout's xd would hold, without that copy.  A masked problem needs ldw == C (the mask index space
+ * is the contiguous [M][C] tensor), a seed and 2^-16 <= p <= 1 - 2^-16; site == CVFT_RANK_UNMASKED marks a plain product (seed
+ * and p ignored), so one launch mixes masked dA = V^T drop(x) with the unmasked dB = dY^T U.  The pair twin masks X only. */
+#define CVFT_RANK_UNMASKED 0xffffffffu
+int cvft_lora_rank_partial_pair_masked(int M, int r, int K, const void* X, int ldx, const void* V, int ldv, float* partA, int rpbA,
+                                       int N, const void* dY, int ldy, const void* U, int ldu, float* partB, int rpbB,
+                                       const int64_t* seed, unsigned site, float p, void* stream);
+typedef struct { cvft_rank_prob prob; const int64_t* seed; unsigned site; float p; } cvft_rank_prob_masked;
+int cvft_lora_rank_partial_multi_masked(int M, int r, int n, const cvft_rank_prob_masked* probs, void* stream);
+typedef struct { cvft_rank_prob_m prob; const int64_t* seed; unsigned site; float p; } cvft_rank_prob_m_masked;
+/* (48 problems per launch) */
+int cvft_lora_rank_partial_batch_masked(int r, int n, const cvft_rank_prob_m_masked* probs, void* stream);
 int cvft_lora_grad_reduce(int ntasks, const void* tasks, int max_blocks_x, void* stream);
 /* One launch per optimiser step: bf16 copy and transposed bf16 copy of every LoRA master in the flat fp32 buffer.
  * tiles: int64[ntiles][6] = {src offset (elements of flat_p), dst ptr, dst_t ptr, rows | cols << 32,
