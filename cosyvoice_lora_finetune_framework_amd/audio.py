@@ -3,8 +3,9 @@
 ``mel_spectrogram`` keeps the reference's signature and layout ([B, 80, T]); ``MelExtractor`` is what the other callers
 use (ragged batches, channel-last output, padding value).  Both run ``cvft_melspec`` (csrc/melspec.hip): one launch from
 samples to log-mel.  Only the CosyVoice-300M setting is built -- 22 050 Hz, n_fft = window = 1024, hop 256, 80 Slaney
-bands over 0 .. 8000 Hz, ``center=False`` -- and every other setting raises ``NotImplementedError`` naming it.
-Resampling is not built: audio at another rate raises.
+bands over 0 .. 8000 Hz, ``center=False`` -- and every other setting raises ``NotImplementedError`` naming it; audio at
+another rate is resampled first, by the caller: ``Resampler`` / ``resample`` run ``cvft_resample`` (csrc/resample.hip), the
+published formula of ``torchaudio.transforms.Resample`` with its defaults (``sinc_kernel``).
 
 ``mel_filterbank`` restates the documented formula of ``librosa.filters.mel`` with its defaults (Slaney scale, Slaney
 area normalisation) in fp64, rounded once to fp32; it is not a copy of librosa's output.
@@ -99,17 +100,29 @@ def live_bins(basis: np.ndarray) -> int:
 
 def check_rate(rate: int) -> None:
     if int(rate) != SAMPLE_RATE:
-        raise NotImplementedError(f"sampling rate {rate} Hz: only {SAMPLE_RATE} Hz audio is built (resampling is not)")
+        raise NotImplementedError(f"sampling rate {rate} Hz: the mel front-end is built for {SAMPLE_RATE} Hz only (resample first: "
+                                  f"audio.resample)")
 
 
 def load_wav(path: str) -> Tuple[torch.Tensor, int]:
-    """16-bit PCM file -> (float32 samples [L] scaled by 1 / 32768, channels averaged; the file's rate)."""
+    """integer PCM file -> (float32 samples [L] in [-1, 1), channels averaged; the file's rate).  16-bit samples are
+    scaled by 1 / 32768, 8-bit unsigned ones by (v - 128) / 128, 24- and 32-bit ones by 2^-23 and 2^-31."""
     with wave.open(path, 'rb') as f:
-        if f.getsampwidth() != 2:
-            raise NotImplementedError(f"{path}: {8 * f.getsampwidth()}-bit samples (only 16-bit PCM is read)")
+        sw = f.getsampwidth()
+        if sw not in (1, 2, 3, 4):
+            raise NotImplementedError(f"{path}: {8 * sw}-bit samples (8-, 16-, 24- and 32-bit integer PCM is read)")
         rate, ch = f.getframerate(), f.getnchannels()
-        pcm = np.frombuffer(f.readframes(f.getnframes()), dtype='<i2')
-    x = pcm.astype(np.float32) / 32768.0
+        raw = f.readframes(f.getnframes())
+    if sw == 2:
+        x = np.frombuffer(raw, dtype='<i2').astype(np.float32) / 32768.0
+    elif sw == 1:
+        x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    elif sw == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        x = (v - ((v & 0x800000) << 1)).astype(np.float32) / 8388608.0           # |v| < 2^24: exact in fp32
+    else:
+        x = (np.frombuffer(raw, dtype='<i4').astype(np.float64) / 2147483648.0).astype(np.float32)
     if ch > 1:
         x = x.reshape(-1, ch).mean(axis=1, dtype=np.float32)
     return torch.from_numpy(np.ascontiguousarray(x)), rate
@@ -183,3 +196,134 @@ def mel_spectrogram(y: torch.Tensor, n_fft: int = N_FFT, num_mels: int = N_MELS,
     if not y.is_cuda:
         raise CvftError("mel_spectrogram needs a ROCm device tensor; there is no CPU fallback")
     return extractor(y.device)(y)
+
+
+# ---------------------------------------------------------------------------------
+# resampling (torchaudio.transforms.Resample with its defaults: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99)
+# ---------------------------------------------------------------------------------
+LOWPASS_WIDTH, ROLLOFF = 6, 0.99
+RESAMPLE_TILE = 2048                          # CVFT_RESAMPLE_TILE (include/cvft.h): output samples per workgroup
+RESAMPLE_MAX_TAPS = 12288                     # CVFT_RESAMPLE_MAX_TAPS: floats of the compact table, n * span
+RESAMPLE_MAX_WINDOW = 16384                   # CVFT_RESAMPLE_MAX_WINDOW: floats of a tile's input window
+
+
+def rate_ratio(orig: int, new: int) -> Tuple[int, int, int]:
+    """(o, n, width): the rates over their gcd, and the filter's half-width in input samples."""
+    orig, new = int(orig), int(new)
+    if orig <= 0 or new <= 0:
+        raise ValueError(f"sampling rates must be positive, got {orig} and {new}")
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    return o, n, int(math.ceil(LOWPASS_WIDTH * o / (min(o, n) * ROLLOFF)))
+
+
+def sinc_kernel(orig: int, new: int) -> Tuple[np.ndarray, int, int, int]:
+    """-> (K fp32 [n, 2 width + o], width, o, n): K[i][k] = sinc(pi t) cos^2(pi t / 12) base / o with
+    t = (-i / n + (k - width) / o) base clamped to [-6, 6] and base = 0.99 min(o, n); fp64, rounded once."""
+    o, n, width = rate_ratio(orig, new)
+    base = min(o, n) * ROLLOFF
+    i = np.arange(n, dtype=np.float64).reshape(-1, 1)
+    k = np.arange(2 * width + o, dtype=np.float64).reshape(1, -1)
+    t = np.clip((-i / n + (k - width) / o) * base, -float(LOWPASS_WIDTH), float(LOWPASS_WIDTH))
+    window = np.cos(np.pi * t / (2.0 * LOWPASS_WIDTH)) ** 2
+    x = np.pi * t
+    sinc = np.where(x == 0.0, 1.0, np.sin(x) / np.where(x == 0.0, 1.0, x))
+    return (sinc * window * (base / o)).astype(np.float32), width, o, n
+
+
+def compact_taps(K: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """dense K [n, cols] -> (first int32 [n], taps fp32 [n, span]): span is the longest first-to-last non-zero run of a
+    row, row i keeps columns first[i] .. first[i] + span - 1 (its run, zero-padded; shifted left where it would pass the
+    table's end)."""
+    n, cols = K.shape
+    nz = K != 0
+    lo = np.where(nz.any(axis=1), nz.argmax(axis=1), 0)
+    hi = np.where(nz.any(axis=1), cols - 1 - nz[:, ::-1].argmax(axis=1), 0)
+    span = int((hi - lo).max()) + 1
+    first = np.minimum(lo, cols - span).astype(np.int32)
+    taps = K[np.arange(n)[:, None], first[:, None] + np.arange(span)[None, :]]
+    return first, np.ascontiguousarray(taps.astype(np.float32))
+
+
+def resampled_length(length: int, orig: int, new: int) -> int:
+    """ceil(new * length / orig): the samples a `length`-sample row resamples to."""
+    g = math.gcd(int(orig), int(new))
+    o, n = int(orig) // g, int(new) // g
+    return (n * int(length) + o - 1) // o
+
+
+def _tile_window(o: int, n: int, width: int) -> int:
+    """padded input samples the outputs of one tile can read (csrc/resample.hip: rs_window)."""
+    return ((RESAMPLE_TILE - 1) // n + 2) * o + 2 * width
+
+
+class Resampler:
+    """`orig` Hz -> `new` Hz.  Holds the compact tap table on `device` once; ``__call__`` is one kernel launch."""
+
+    def __init__(self, orig: int, new: int, device: Union[str, torch.device] = 'cuda'):
+        self.orig, self.new, self.device = int(orig), int(new), torch.device(device)
+        self.o, self.n, self.width = rate_ratio(orig, new)
+        self.span, self.first, self.taps = 0, None, None
+        if self.orig == self.new:
+            return
+        refuse = lambda what: NotImplementedError(                                                     # noqa: E731
+            f"resampling {self.orig} Hz -> {self.new} Hz: {what} (o = {self.o}, n = {self.n} after the gcd)")
+        # a row's run covers |t| < 6, an interval 12 o / base > 2 width - 2 columns long that holds at least 2 width - 3 of
+        # them: refuse before building a huge dense table
+        if self.n * (2 * self.width - 3) > RESAMPLE_MAX_TAPS:
+            raise refuse(f"the tap table needs more than n * (2 width - 3) = {self.n * (2 * self.width - 3)} floats, "
+                         f"the kernel holds {RESAMPLE_MAX_TAPS}")
+        if _tile_window(self.o, self.n, self.width) > RESAMPLE_MAX_WINDOW:
+            raise refuse(f"a tile reads {_tile_window(self.o, self.n, self.width)} input samples, the kernel holds "
+                         f"{RESAMPLE_MAX_WINDOW}")
+        first, taps = compact_taps(sinc_kernel(orig, new)[0])
+        self.span = int(taps.shape[1])
+        if self.n * self.span > RESAMPLE_MAX_TAPS:
+            raise refuse(f"the tap table is n * span = {self.n * self.span} floats, the kernel holds {RESAMPLE_MAX_TAPS}")
+        self.first, self.taps = torch.from_numpy(first).to(self.device), torch.from_numpy(taps).to(self.device)
+
+    def __call__(self, wav: torch.Tensor, lengths: Optional[Sequence[int]] = None):
+        """wav [B, Lmax] (or [L]) fp32 on the device, `lengths` the rows' sample counts (default: Lmax each) ->
+        (out [B, Mmax] fp32, out_lengths): row b holds out_lengths[b] = ceil(new lengths[b] / orig) samples and zeros
+        after them, Mmax = max(out_lengths).  With orig == new the input and `lengths` come back untouched."""
+        from .hipops import functional as HF
+        if self.orig == self.new:
+            return wav, lengths
+        if wav.dim() == 1:
+            wav = wav.unsqueeze(0)
+        if wav.dim() != 2:
+            raise ValueError(f"wav must be [B, L] or [L], got {tuple(wav.shape)}")
+        B, Lmax = wav.shape
+        lens = [Lmax] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if len(lens) != B:
+            raise ValueError(f"{len(lens)} lengths for {B} rows")
+        for i, v in enumerate(lens):
+            if v < 1 or v > Lmax:
+                raise ValueError(f"row {i}: {v} samples outside [1, {Lmax}]")
+        out_lens = [resampled_length(v, self.orig, self.new) for v in lens]
+        out = HF.resample(wav, lens, self.o, self.n, self.width, self.span, self.first, self.taps, max(out_lens))
+        return out, out_lens
+
+
+_RESAMPLERS = {}
+
+
+def resampler(orig: int, new: int, device) -> Resampler:
+    """one Resampler per (orig, new, device), built on first use."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (int(orig), int(new), device)
+    if key not in _RESAMPLERS:
+        _RESAMPLERS[key] = Resampler(orig, new, device)
+    return _RESAMPLERS[key]
+
+
+def resample(wav: torch.Tensor, orig: int, new: int, lengths: Optional[Sequence[int]] = None):
+    """wav [B, L] or [L] on the device at `orig` Hz -> (out [B, Mmax] at `new` Hz, out_lengths); see Resampler."""
+    if int(orig) == int(new):
+        return wav, lengths
+    from .hipops.binding import CvftError
+    if not wav.is_cuda:
+        raise CvftError("resample needs a ROCm device tensor; there is no CPU fallback")
+    return resampler(orig, new, wav.device)(wav, lengths)

@@ -197,6 +197,7 @@ SIGNATURES = {
     "cvft_hift_stft": [_i, _i, _p, _p, _p],
     "cvft_hift_istft": [_i, _i, _p, _i, _f, _p, _p, _p],
     "cvft_melspec": [_i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p, _p],
+    "cvft_resample": [_i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p],
 }
 
 _lib: Optional[C.CDLL] = None

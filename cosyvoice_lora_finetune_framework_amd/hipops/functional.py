@@ -2441,3 +2441,18 @@ def melspec(wav: torch.Tensor, lengths: Sequence[int], dft_tab: torch.Tensor, ba
     check(lib().cvft_melspec(B, Lmax, Lmax, ptr(wav), ptr(ln), ptr(dft_tab), ptr(basis_tab), nchunks, Tmax,
                              1 if channel_last else 0, pad_value, ptr(out), stream()), "cvft_melspec")
     return out
+
+
+def resample(wav: torch.Tensor, lengths: Sequence[int], o: int, n: int, width: int, span: int, first: torch.Tensor,
+             taps: torch.Tensor, Mmax: int) -> torch.Tensor:
+    """cvft_resample: wav [B, Lmax] fp32 with per-row sample counts -> [B, Mmax], row b holding ceil(n lengths[b] / o)
+    samples and zeros after them; `first` / `taps` come from audio.compact_taps (audio.Resampler holds them)."""
+    if not wav.is_cuda:
+        raise cb.CvftError("libcvft ops need ROCm device tensors; there is no CPU fallback")
+    wav = _c(wav.float())
+    B, Lmax = wav.shape
+    ln = torch.tensor([int(v) for v in lengths], dtype=torch.int32).to(wav.device)
+    out = torch.empty((B, Mmax), dtype=torch.float32, device=wav.device)
+    check(lib().cvft_resample(B, Lmax, Lmax, ptr(wav), ptr(ln), o, n, width, span, ptr(first), ptr(taps), Mmax, ptr(out),
+                              stream()), "cvft_resample")
+    return out

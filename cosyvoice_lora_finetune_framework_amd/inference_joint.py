@@ -5,7 +5,7 @@ without the text front-end.
     python -m cosyvoice_lora_finetune_framework_amd.inference_joint --llm merged/llm.pt --flow merged/flow.pt \\
         --text-tokens 12,873,44,9 --out mel.npy [--speed 0.9] [--seed 0] [--dtype bf16]
         [--top-p 0.8 --top-k 25 --win-size 10 --tau-r 0.1] [--llm-config '{...}' --flow-config '{...}'] [--noise z.npy]
-        [--hift hift.pt --wav out.wav [--hift-dtype fp32] [--hift-seed 0]]
+        [--hift hift.pt --wav out.wav [--wav-rate 22050] [--hift-dtype fp32] [--hift-seed 0]]
         [--prompt-wav p.wav --prompt-tokens 5,9,.. --prompt-text-tokens 3,4,.. --embedding e.npy]
 
 ``--llm`` / ``--flow`` are the merged state_dicts ``merge_joint_weights.py`` writes; ``--text-tokens`` is a comma-separated
@@ -15,8 +15,10 @@ The LLM samples with ``utils.ras_sampling`` and the given parameters (``--top-k 
 of other dimensions than CosyVoice-300M; ``--noise`` pins the Flow's initial noise ([1, 80, T] ``.npy``).
 ``--hift`` is the HiFT generator's state_dict (``hift.pt``); with it the mel also goes through ``hift.HiFTGenerator`` and
 ``--wav`` is written as 16-bit PCM at 22 050 Hz.  ``--hift-dtype`` is the vocoder's weight dtype (fp32 by default),
-``--hift-seed`` pins its source's random phase and noise.  Without ``--hift`` only the mel is written.
-``--prompt-wav`` (16-bit PCM at 22 050 Hz) is turned into the Flow's prompt mel on the GPU (``audio.MelExtractor``);
+``--hift-seed`` pins its source's random phase and noise; ``--wav-rate`` resamples the waveform on the GPU
+(``audio.Resampler``) before it is written.  Without ``--hift`` only the mel is written.
+``--prompt-wav`` (integer PCM at any rate; resampled to 22 050 Hz on the GPU when it is at another) is turned into the
+Flow's prompt mel on the GPU (``audio.MelExtractor``);
 ``--prompt-tokens`` / ``--prompt-text-tokens`` are the prompt's speech and text token ids (they come from the reference's
 tokenizers, which are not rebuilt here) and ``--embedding`` its speaker embedding.  Without them the prompt is empty.
 """
@@ -40,10 +42,11 @@ from .config import MEL_MEAN, MEL_STD
 @torch.no_grad()
 def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] = None,
                noise: Optional[torch.Tensor] = None, *, prompt_wav: Optional[torch.Tensor] = None,
-               prompt_speech_token=None, prompt_text=None, embedding: Optional[torch.Tensor] = None
-               ) -> Tuple[List[int], torch.Tensor]:
+               prompt_speech_token=None, prompt_text=None, embedding: Optional[torch.Tensor] = None,
+               prompt_rate: Optional[int] = None) -> Tuple[List[int], torch.Tensor]:
     """-> (speech tokens, de-normalised mel (1, 80, T) fp32).  `seed` pins the LLM's sampler, `noise` the Flow's
-    initial z.  Zero-shot prompting: `prompt_wav` (samples at 22 050 Hz) becomes the Flow's `prompt_feat` -- its log-mel
+    initial z.  Zero-shot prompting: `prompt_wav` (samples at 22 050 Hz, or at `prompt_rate` Hz: then it is resampled to
+    22 050 Hz first, audio.Resampler) becomes the Flow's `prompt_feat` -- its log-mel
     (audio.MelExtractor), normalised with MEL_MEAN / MEL_STD as the reference's patched flow inference does for a
     non-empty prompt --, `prompt_speech_token` goes to both models, `prompt_text` to the LLM, `embedding` (1, 192) to
     both.  With none of them the prompt is empty and the embedding zero."""
@@ -57,8 +60,11 @@ def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] =
     if prompt_wav is None:
         p_feat = torch.zeros(1, 0, 80, device=dev)
     else:
-        from .audio import extractor
-        p_feat = (extractor(dev)(prompt_wav.float().reshape(1, -1).to(dev), channel_last=True) - MEL_MEAN) / MEL_STD
+        from .audio import SAMPLE_RATE, extractor, resample
+        p_wav = prompt_wav.float().reshape(1, -1).to(dev)
+        if prompt_rate is not None and int(prompt_rate) != SAMPLE_RATE:
+            p_wav, _ = resample(p_wav, prompt_rate, SAMPLE_RATE)
+        p_feat = (extractor(dev)(p_wav, channel_last=True) - MEL_MEAN) / MEL_STD
     n = lambda t: torch.tensor([t.shape[1]])                                                           # noqa: E731
     tokens = list(llm.inference(text, n(text), p_text, n(p_text), p_tok, n(p_tok), emb, seed=seed))
     if not tokens:
@@ -116,12 +122,13 @@ def main(argv=None):
     ap.add_argument('--llm-config', default='{}', help='JSON keyword arguments of build_llm_model')
     ap.add_argument('--flow-config', default='{}', help='JSON keyword arguments of build_flow_model')
     ap.add_argument('--noise', default=None, help='.npy of the Flow\'s initial noise [1, 80, T]')
-    ap.add_argument('--prompt-wav', default=None, help='zero-shot prompt: 16-bit PCM at 22 050 Hz (its mel conditions the Flow)')
+    ap.add_argument('--prompt-wav', default=None, help='zero-shot prompt: integer PCM at any rate (its mel conditions the Flow)')
     ap.add_argument('--prompt-tokens', default=None, help='the prompt\'s speech token ids (comma-separated or .npy)')
     ap.add_argument('--prompt-text-tokens', default=None, help='the prompt\'s text token ids (comma-separated or .npy)')
     ap.add_argument('--embedding', default=None, help='.npy of the speaker embedding (192 floats); default zero')
     ap.add_argument('--hift', default=None, help='HiFT generator state_dict (hift.pt): also vocode the mel')
-    ap.add_argument('--wav', default='out.wav', help='with --hift: the waveform, 16-bit PCM at 22 050 Hz')
+    ap.add_argument('--wav', default='out.wav', help='with --hift: the waveform, 16-bit PCM at --wav-rate')
+    ap.add_argument('--wav-rate', type=int, default=22050, help='rate of --wav; other than 22050: resampled on the GPU')
     ap.add_argument('--hift-dtype', choices=('fp32', 'bf16'), default='fp32')
     ap.add_argument('--hift-seed', type=int, default=None)
     a = ap.parse_args(argv)
@@ -137,10 +144,8 @@ def main(argv=None):
     noise = torch.from_numpy(np.load(a.noise)).float().to(dev) if a.noise else None
     prompt = {}
     if a.prompt_wav:
-        from .audio import check_rate, load_wav
-        wav, rate = load_wav(a.prompt_wav)
-        check_rate(rate)
-        prompt['prompt_wav'] = wav
+        from .audio import load_wav
+        prompt['prompt_wav'], prompt['prompt_rate'] = load_wav(a.prompt_wav)
     if a.prompt_tokens:
         prompt['prompt_speech_token'] = _text_tokens(a.prompt_tokens)
     if a.prompt_text_tokens:
@@ -155,8 +160,11 @@ def main(argv=None):
         voc = HiFTGenerator(dtype=torch.bfloat16 if a.hift_dtype == 'bf16' else torch.float32)
         voc.load_state_dict(torch.load(a.hift, map_location='cpu', weights_only=True), strict=True)
         wav = vocode(voc.to(dev).eval(), mel, seed=a.hift_seed)
-        write_wav(a.wav, wav[0], voc.sampling_rate)
-        print(f"mel -> {wav.shape[1]} samples at {voc.sampling_rate} Hz -> {a.wav}")
+        if a.wav_rate != voc.sampling_rate:
+            from .audio import resample
+            wav, _ = resample(wav, voc.sampling_rate, a.wav_rate)
+        write_wav(a.wav, wav[0], a.wav_rate)
+        print(f"mel -> {wav.shape[1]} samples at {a.wav_rate} Hz -> {a.wav}")
 
 
 if __name__ == '__main__':

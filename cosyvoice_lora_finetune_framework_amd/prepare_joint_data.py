@@ -9,6 +9,10 @@ manifest's directory), ``text``, ``text_token``, ``speech_token`` (id lists) and
 reference computes those three with its text tokenizer and two ONNX models (speech tokenizer, speaker encoder), which
 this project does not rebuild, so they come precomputed; what is computed here is ``speech_feat``,
 the [T, 80] log-mel the Flow is trained on, on the GPU (``audio.MelExtractor``) in length-sorted ragged batches.
+Files that are not at 22 050 Hz are resampled to it on the GPU first (``audio.Resampler``), as the reference does with
+torchaudio (prepare_joint_data.py:172-174).  ``--resampled-dir`` with ``--resampled-rate`` also writes every kept
+utterance resampled to that rate as ``<utt>.wav`` (16-bit PCM): 16 000 Hz is what the reference's speech tokenizer and
+speaker encoder take, so their inputs need no other tool.
 
 Like the reference (prepare_joint_data.py:252-256) utterances shorter than 0.5 s or longer than 30 s are dropped.
 Output: ``data_%06d.parquet`` with the reference's columns -- utt, text, text_token, speech_token, speech_feat
@@ -20,7 +24,7 @@ import argparse
 import json
 import os
 import wave
-from typing import Any, Dict, List, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
@@ -75,25 +79,44 @@ def filter_entries(entries: List[Dict[str, Any]], verbose: bool = True) -> List[
     return kept
 
 
-def extract_feats(entries: List[Dict[str, Any]], device, batch: int = 16) -> List[torch.Tensor]:
-    """speech_feat [T, 80] (CPU fp32) per entry, in the entries' order; batches are formed after sorting by length."""
+def _batches(wavs: List[torch.Tensor], rates: List[int], batch: int):
+    """(rate, entry indices, lengths, zero-padded [rows, max length] CPU tensor) per batch: one source rate per batch,
+    batches formed after sorting by length."""
+    for rate in sorted(set(rates)):
+        order = sorted((i for i in range(len(wavs)) if rates[i] == rate), key=lambda i: wavs[i].shape[0])
+        for i0 in range(0, len(order), batch):
+            idx = order[i0:i0 + batch]
+            lens = [wavs[i].shape[0] for i in idx]
+            pad = torch.zeros(len(idx), max(lens))
+            for r, i in enumerate(idx):
+                pad[r, :lens[r]] = wavs[i]
+            yield rate, idx, lens, pad
+
+
+def extract_feats(entries: List[Dict[str, Any]], device, batch: int = 16, resampled_dir: Optional[str] = None,
+                  resampled_rate: Optional[int] = None) -> List[torch.Tensor]:
+    """speech_feat [T, 80] (CPU fp32) per entry, in the entries' order.  Files at another rate than 22 050 Hz are
+    resampled to it on the GPU, batched per source rate; with `resampled_dir` every entry is also written there as
+    <utt>.wav at `resampled_rate`."""
     ext = A.extractor(device)
-    wavs = []
+    wavs, rates = [], []
     for e in entries:
         w, rate = A.load_wav(e["wav"])
-        A.check_rate(rate)
         wavs.append(w)
-    order = sorted(range(len(wavs)), key=lambda i: wavs[i].shape[0])
+        rates.append(int(rate))
     feats: List[Any] = [None] * len(wavs)
-    for i0 in range(0, len(order), batch):
-        idx = order[i0:i0 + batch]
-        lens = [wavs[i].shape[0] for i in idx]
-        pad = torch.zeros(len(idx), max(lens))
+    for rate, idx, lens, pad in _batches(wavs, rates, batch):
+        x = pad.to(device)
+        y, ylens = A.resample(x, rate, A.SAMPLE_RATE, lens)
+        mel = ext(y, ylens, channel_last=True).cpu()
         for r, i in enumerate(idx):
-            pad[r, :lens[r]] = wavs[i]
-        mel = ext(pad.to(device), lens, channel_last=True).cpu()
-        for r, i in enumerate(idx):
-            feats[i] = mel[r, :A.n_frames(lens[r])].contiguous()
+            feats[i] = mel[r, :A.n_frames(ylens[r])].contiguous()
+        if resampled_dir is not None:
+            from .inference_joint import write_wav
+            z, zlens = A.resample(x, rate, resampled_rate, lens)
+            z = z.cpu()
+            for r, i in enumerate(idx):
+                write_wav(os.path.join(resampled_dir, f"{entries[i]['utt']}.wav"), z[r, :zlens[r]], int(resampled_rate))
     return feats
 
 
@@ -113,16 +136,20 @@ def write_shard(rows: List[Dict[str, Any]], output_dir: str, index: int) -> str:
 
 
 def prepare(manifest: str, output_dir: str, samples_per_file: int = 100, batch: int = 16, device="cuda",
-            verbose: bool = True) -> List[str]:
+            verbose: bool = True, resampled_dir: Optional[str] = None, resampled_rate: Optional[int] = None) -> List[str]:
     """-> the shard paths written (also listed in output_dir/data.list)."""
+    if (resampled_dir is None) != (resampled_rate is None):
+        raise ValueError("--resampled-dir and --resampled-rate go together")
     os.makedirs(output_dir, exist_ok=True)
+    if resampled_dir is not None:
+        os.makedirs(resampled_dir, exist_ok=True)
     entries = filter_entries(read_manifest(manifest), verbose)
     if not entries:
         raise RuntimeError(f"{manifest}: no utterance left after the duration filter")
     shards = []
     for i0 in range(0, len(entries), samples_per_file):
         part = entries[i0:i0 + samples_per_file]
-        rows = [make_row(e, f) for e, f in zip(part, extract_feats(part, device, batch))]
+        rows = [make_row(e, f) for e, f in zip(part, extract_feats(part, device, batch, resampled_dir, resampled_rate))]
         shards.append(write_shard(rows, output_dir, len(shards)))
         if verbose:
             print(f"  wrote {shards[-1]} ({len(rows)} utterances)")
@@ -138,8 +165,11 @@ def main(argv=None):
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--samples-per-file", type=int, default=100)
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--resampled-dir", default=None, help="also write every kept utterance here as <utt>.wav at --resampled-rate")
+    ap.add_argument("--resampled-rate", type=int, default=None, help="rate of the files in --resampled-dir, e.g. 16000")
     a = ap.parse_args(argv)
-    shards = prepare(a.manifest, a.output_dir, a.samples_per_file, a.batch)
+    shards = prepare(a.manifest, a.output_dir, a.samples_per_file, a.batch, resampled_dir=a.resampled_dir,
+                     resampled_rate=a.resampled_rate)
     print(f"{len(shards)} shard(s) -> {os.path.join(a.output_dir, 'data.list')}")
 
 

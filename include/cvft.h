@@ -640,6 +640,31 @@ int cvft_hift_istft(int B, int F, const float* x, int ldx, float limit, float* w
 int cvft_melspec(int B, int Lmax, int ldw, const float* wav, const int* len, const float* dft_tab, const float* basis_tab,
                  int nchunks, int Tmax, int channel_last, float pad_value, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Resampler (torchaudio.transforms.Resample with its defaults -- sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99 --
+ * as the reference applies it to every wav before feature extraction; resample.hip).  One launch, no atomics,
+ * bit-identical run to run and row by row.
+ *
+ * cvft_resample: wav [B][ldw] fp32 (row b holds len[b] <= Lmax samples; len == NULL: every row holds Lmax) -> out [B][Mmax];
+ *   row b gets M_b = min(ceil(n len[b] / o), Mmax) samples and zeros after them.  o = orig / gcd, n = new / gcd,
+ *   width = ceil(6 o / (0.99 min(o, n))).  With xp[m] = x[m - width] inside the row and 0 outside it,
+ *   out[j n + i] = sum_{k < span} taps[i][k] * xp[j o + first[i] + k], fp32 FMAs in ascending k.
+ *   taps [n][span] fp32 and first [n] int are the compact form of the dense [n][2 width + o] filter table: every dense row
+ *   is zero outside a run of at most 2 width + 1 columns, span is the longest run, row i keeps columns first[i] ..
+ *   first[i] + span - 1 (0 <= first[i] <= 2 width + o - span; the kernel clamps it into that range).
+ *   (audio.py: sinc_kernel / compact_taps build them.)
+ *   A workgroup owns CVFT_RESAMPLE_TILE consecutive output samples of one row and stages the table and its input window in
+ *   LDS.  Refused, with nothing launched: B outside [1, 65535]; span outside [1, 2 width + 1]; n * span above
+ *   CVFT_RESAMPLE_MAX_TAPS floats (48 KB); a tile's window ((CVFT_RESAMPLE_TILE - 1) / n + 2) o + 2 width above
+ *   CVFT_RESAMPLE_MAX_WINDOW floats (64 KB: o / n up to about 7.9); more than 128 KB of LDS in all; Lmax or Mmax above 2^30,
+ *   or a padded sample index (Mmax / n + 2) o + 2 width at or above 2^31.
+ * ------------------------------------------------------------------------------- */
+#define CVFT_RESAMPLE_TILE 2048
+#define CVFT_RESAMPLE_MAX_TAPS 12288
+#define CVFT_RESAMPLE_MAX_WINDOW 16384
+int cvft_resample(int B, int Lmax, int ldw, const float* wav, const int* len, int o, int n, int width, int span,
+                  const int* first, const float* taps, int Mmax, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
