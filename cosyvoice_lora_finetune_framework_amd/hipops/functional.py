@@ -2456,3 +2456,83 @@ def resample(wav: torch.Tensor, lengths: Sequence[int], o: int, n: int, width: i
     check(lib().cvft_resample(B, Lmax, Lmax, ptr(wav), ptr(ln), o, n, width, span, ptr(first), ptr(taps), Mmax, ptr(out),
                               stream()), "cvft_resample")
     return out
+
+
+def stream_mel_stitch(x: torch.Tensor, trim: int, ov: int, window: Optional[torch.Tensor], prev: Optional[torch.Tensor] = None,
+                      cache: Optional[torch.Tensor] = None, finalize: bool = False, scale_shift=None, cache_len: int = 0):
+    """cvft_stream_mel_stitch: the chunk's Flow output x [C, Tn] fp32 -> (vocoder input [C, mc + Tn - trim - (0 if finalize
+    else ov)], new overlap [C, ov] or None when finalising, new cached mel = the last min(cache_len, columns) columns of
+    the vocoder input, or None with cache_len == 0).  prev [C, >= ov]: the previous overlap, its last ov columns are faded
+    out under window [2 ov] while the chunk's first ov fade in; cache [C, mc]: the vocoder's cached mel, prepended;
+    scale_shift = (scale, shift): x * scale + shift first.  A chunk shorter than the overlap after trimming is refused on
+    the host with a ValueError that names the lengths."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"x must be [C, Tn] fp32, got {tuple(x.shape)} {x.dtype}")
+    C_, Tn = x.shape
+    trim, ov = int(trim), int(ov)
+    if not 0 <= trim < max(Tn, 1):
+        raise ValueError(f"trim {trim} outside the chunk of {Tn} columns")
+    if prev is not None and prev.shape[-1] == 0:
+        prev = None
+    if cache is not None and cache.shape[-1] == 0:
+        cache = None
+    if Tn - trim < ov and not (finalize and prev is None):      # (a whole utterance in one final chunk may be shorter)
+        raise ValueError(f"chunk too short to stitch: {Tn} columns - {trim} trimmed = {Tn - trim}, below the overlap of {ov}")
+    if not x.is_cuda:
+        raise cb.CvftError("libcvft ops need ROCm device tensors; there is no CPU fallback")
+    if prev is not None and (prev.dim() != 2 or prev.shape[0] != C_ or prev.shape[1] < ov or ov < 1):
+        raise ValueError(f"previous overlap {tuple(prev.shape)} for {C_} channels and an overlap of {ov}")
+    if cache is not None and (cache.dim() != 2 or cache.shape[0] != C_):
+        raise ValueError(f"cached mel {tuple(cache.shape)} for {C_} channels")
+    if prev is not None and (window is None or window.numel() != 2 * ov):
+        raise ValueError(f"the window must hold 2 * {ov} values")
+    x = x if x.stride(1) == 1 and x.stride(0) >= Tn else x.contiguous()       # (a column slice of the Flow's output as it is)
+    prev = None if prev is None else _c(prev.float())
+    cache = None if cache is None else _c(cache.float())
+    window = None if window is None else _c(window.float())
+    mc = 0 if cache is None else cache.shape[1]
+    Tout = mc + Tn - trim - (0 if finalize else ov)
+    out = torch.empty((C_, Tout), dtype=torch.float32, device=x.device)
+    nov = None if finalize else torch.empty((C_, ov), dtype=torch.float32, device=x.device)
+    mc_out = min(int(cache_len), Tout)
+    ncache = torch.empty((C_, mc_out), dtype=torch.float32, device=x.device) if mc_out > 0 else None
+    sc, sh = (float(scale_shift[0]), float(scale_shift[1])) if scale_shift is not None else (1.0, 0.0)
+    check(lib().cvft_stream_mel_stitch(C_, Tn, x.stride(0), ptr(x), trim, 1 if scale_shift is not None else 0, sc, sh, ov,
+                                       ptr(prev), prev.stride(0) if prev is not None else 0,
+                                       prev.shape[1] if prev is not None else 0, mc, ptr(cache),
+                                       cache.stride(0) if cache is not None else 0, ptr(window), 1 if finalize else 0,
+                                       ptr(out), max(out.stride(0), Tout), ptr(nov), ptr(ncache), mc_out, stream()),
+          "cvft_stream_mel_stitch")
+    return out, nov, ncache
+
+
+def stream_wav_stitch(speech: torch.Tensor, sc: int, window: Optional[torch.Tensor], cache: Optional[torch.Tensor] = None,
+                      finalize: bool = False, want_pcm: bool = False):
+    """cvft_stream_wav_stitch: the vocoder's speech [N] fp32 -> (emitted samples [N - (0 if finalize else sc)], new speech
+    cache [sc] or None when finalising, the emitted samples as int16 PCM or None).  cache [sc]: the previous chunk's
+    withheld tail, faded out under window [2 sc] while the first sc samples fade in."""
+    if speech.dim() != 1 or speech.dtype != torch.float32:
+        raise ValueError(f"speech must be [N] fp32, got {tuple(speech.shape)} {speech.dtype}")
+    N, sc = speech.shape[0], int(sc)
+    if cache is not None and cache.numel() == 0:
+        cache = None
+    if finalize and cache is None:
+        sc = 0                                                       # nothing to fade, nothing withheld: a copy
+    if N < sc:
+        raise ValueError(f"speech too short to stitch: {N} samples, below the cache of {sc}")
+    if not speech.is_cuda:
+        raise cb.CvftError("libcvft ops need ROCm device tensors; there is no CPU fallback")
+    if cache is not None and (cache.numel() != sc or window is None or window.numel() != 2 * sc):
+        raise ValueError(f"speech cache of {cache.numel()} samples and a window of {0 if window is None else window.numel()} "
+                         f"for a cache length of {sc}")
+    speech = _c(speech)
+    cache = None if cache is None else _c(cache.float().reshape(-1))
+    window = None if window is None else _c(window.float())
+    Nout = N - (0 if finalize else sc)
+    out = torch.empty((Nout,), dtype=torch.float32, device=speech.device)
+    ncache = None if finalize else torch.empty((sc,), dtype=torch.float32, device=speech.device)
+    pcm = torch.empty((Nout,), dtype=torch.int16, device=speech.device) if want_pcm else None
+    if N > 0:
+        check(lib().cvft_stream_wav_stitch(N, ptr(speech), sc, ptr(cache), ptr(window), 1 if finalize else 0, ptr(out),
+                                           ptr(ncache), ptr(pcm), stream()), "cvft_stream_wav_stitch")
+    return out, ncache, pcm

@@ -7,6 +7,7 @@ without the text front-end.
         [--top-p 0.8 --top-k 25 --win-size 10 --tau-r 0.1] [--llm-config '{...}' --flow-config '{...}'] [--noise z.npy]
         [--hift hift.pt --wav out.wav [--wav-rate 22050] [--hift-dtype fp32] [--hift-seed 0]]
         [--prompt-wav p.wav --prompt-tokens 5,9,.. --prompt-text-tokens 3,4,.. --embedding e.npy]
+        [--stream [--token-hop 100]]
 
 ``--llm`` / ``--flow`` are the merged state_dicts ``merge_joint_weights.py`` writes; ``--text-tokens`` is a comma-separated
 id list or a ``.npy`` file of ids.  The mel is de-normalised with MEL_MEAN / MEL_STD and written as [80, T] float32.
@@ -21,6 +22,10 @@ of other dimensions than CosyVoice-300M; ``--noise`` pins the Flow's initial noi
 Flow's prompt mel on the GPU (``audio.MelExtractor``);
 ``--prompt-tokens`` / ``--prompt-text-tokens`` are the prompt's speech and text token ids (they come from the reference's
 tokenizers, which are not rebuilt here) and ``--embedding`` its speaker embedding.  Without them the prompt is empty.
+``--stream`` (needs ``--hift``) synthesises chunk by chunk while the LLM keeps decoding (``streaming.StreamingSynthesizer``,
+the reference's ``tts(stream=True)``): each chunk is appended to ``--wav`` as it arrives, the time to the first chunk and
+the total time are printed and no mel file is written.  ``--token-hop`` is the number of new speech tokens per chunk
+(default 2 x the Flow's token rate).  ``--wav-rate`` must stay 22050 with it: the resampler keeps no state between chunks.
 """
 from __future__ import annotations
 
@@ -131,7 +136,18 @@ def main(argv=None):
     ap.add_argument('--wav-rate', type=int, default=22050, help='rate of --wav; other than 22050: resampled on the GPU')
     ap.add_argument('--hift-dtype', choices=('fp32', 'bf16'), default='fp32')
     ap.add_argument('--hift-seed', type=int, default=None)
+    ap.add_argument('--stream', action='store_true', help='with --hift: synthesise chunk by chunk, appending to --wav')
+    ap.add_argument('--token-hop', type=int, default=None, help='with --stream: new speech tokens per chunk')
     a = ap.parse_args(argv)
+    if a.stream and not a.hift:
+        ap.error('--stream needs --hift: a streamed chunk is a piece of the waveform')
+    if a.stream and a.wav_rate != 22050:
+        ap.error('--stream writes at 22050 Hz only: the resampler keeps no state from one chunk to the next, '
+                 'so --wav-rate %d cannot be combined with it' % a.wav_rate)
+    if a.stream and a.noise:
+        ap.error('--noise pins one initial noise tensor; with --stream every chunk draws its own (use --seed / torch.manual_seed)')
+    if a.token_hop is not None and not a.stream:
+        ap.error('--token-hop is an option of --stream')
     num = Numerics(dtype=torch.bfloat16 if a.dtype == 'bf16' else torch.float32)
     kw = lambda js: {k: tuple(v) if isinstance(v, list) else v for k, v in json.loads(js).items()}   # noqa: E731
     llm = build_llm_model(None, 'cpu', numerics=num, **kw(a.llm_config))
@@ -152,6 +168,8 @@ def main(argv=None):
         prompt['prompt_text'] = _text_tokens(a.prompt_text_tokens)
     if a.embedding:
         prompt['embedding'] = torch.from_numpy(np.load(a.embedding)).float()
+    if a.stream:
+        return _stream_main(a, llm, flow, dev, prompt)
     tokens, mel = synthesize(llm, flow, _text_tokens(a.text_tokens), a.speed, a.seed, noise=noise, **prompt)
     np.save(a.out, mel[0].cpu().numpy().astype(np.float32))
     print(f"{len(tokens)} speech tokens -> mel {tuple(mel.shape[1:])} -> {a.out}")
@@ -165,6 +183,33 @@ def main(argv=None):
             wav, _ = resample(wav, voc.sampling_rate, a.wav_rate)
         write_wav(a.wav, wav[0], a.wav_rate)
         print(f"mel -> {wav.shape[1]} samples at {a.wav_rate} Hz -> {a.wav}")
+
+
+def _stream_main(a, llm, flow, dev, prompt):
+    """--stream: chunks go to --wav as they arrive (16-bit PCM converted on the device by the stitch launch)."""
+    import time
+    from .hift import HiFTGenerator
+    from .streaming import SPEED_MSG, StreamingSynthesizer
+    if a.speed != 1.0:
+        raise SystemExit(SPEED_MSG)
+    voc = HiFTGenerator(dtype=torch.bfloat16 if a.hift_dtype == 'bf16' else torch.float32)
+    voc.load_state_dict(torch.load(a.hift, map_location='cpu', weights_only=True), strict=True)
+    syn = StreamingSynthesizer(llm, flow, voc.to(dev).eval(), token_hop_len=a.token_hop)
+    torch.cuda.synchronize(dev)
+    t0, first, n, chunks = time.perf_counter(), None, 0, 0
+    with wave.open(a.wav, 'wb') as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(voc.sampling_rate)
+        for item in syn.tts(_text_tokens(a.text_tokens), stream=True, seed=a.seed, hift_seed=a.hift_seed,
+                            want_pcm=True, **prompt):
+            pcm = item['pcm'].cpu().numpy().astype('<i2')
+            first = time.perf_counter() - t0 if first is None else first
+            f.writeframes(pcm.tobytes())
+            n, chunks = n + pcm.shape[0], chunks + 1
+    total = time.perf_counter() - t0
+    print(f"{chunks} chunks -> {n} samples at {voc.sampling_rate} Hz -> {a.wav}")
+    print(f"first chunk after {first * 1e3:.1f} ms, total {total * 1e3:.1f} ms")
 
 
 if __name__ == '__main__':

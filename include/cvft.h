@@ -665,6 +665,33 @@ int cvft_melspec(int B, int Lmax, int ldw, const float* wav, const int* len, con
 int cvft_resample(int B, int Lmax, int ldw, const float* wav, const int* len, int o, int n, int width, int span,
                   const int* first, const float* taps, int Mmax, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Streaming synthesis (cosyvoice/cli/model.py CosyVoiceModel.token2wav; stream.hip): what joins consecutive chunks, each
+ * side in one elementwise launch.  No LDS, no atomics, one writer per output element, bit-identical run to run.
+ * A fade is in * w[j] + out * w[n + j] over a window w of 2 n fp32 values, summed in fp64 and rounded once to fp32 (the
+ * reference multiplies by a float64 window).
+ *
+ * cvft_stream_mel_stitch: the chunk's Flow output x [C][ldx] (Tn columns) -> the vocoder's input mel and the state kept
+ *   for the next chunk.  y = x[:, trim:], times scale plus shift when affine != 0 (a rounded product, then a rounded sum:
+ *   bit-equal to torch's x * scale + shift); with prev != NULL the first ov columns of y are faded against the LAST ov of
+ *   prev's prev_cols columns (pitch ldp); cat = [cache [C][ldc] (mc columns; NULL with mc == 0) | y].
+ *   finalize == 0: out [C][ldo] = cat without its last ov columns, new_overlap [C][ov] = those columns.
+ *   finalize != 0: out = cat, new_overlap is not written.
+ *   new_cache [C][mc_out] (or NULL) = the last mc_out columns of out.  Every column outside the fade is a bit-exact copy
+ *   (of the affine result when affine != 0).  Refused, with nothing launched: Tn - trim < ov unless the chunk is final and
+ *   has no prev (a whole utterance in one chunk), and inconsistent shapes.
+ *
+ * cvft_stream_wav_stitch: the vocoder's speech [N] -> with cache != NULL its first sc samples faded against cache [sc]
+ *   over window [2 sc]; finalize == 0: out = the first N - sc samples, new_cache [sc] = the rest; finalize != 0: out =
+ *   all N.  pcm (or NULL): out as 16-bit PCM, clip(rint(out * 32767)) with round half to even.  Refused: N < sc.
+ * ------------------------------------------------------------------------------- */
+int cvft_stream_mel_stitch(int C, int Tn, int ldx, const float* x, int trim, int affine, float scale, float shift, int ov,
+                           const float* prev, int ldp, int prev_cols, int mc, const float* cache, int ldc,
+                           const float* window, int finalize, float* out, int ldo, float* new_overlap, float* new_cache,
+                           int mc_out, void* stream);
+int cvft_stream_wav_stitch(int N, const float* speech, int sc, const float* cache, const float* window, int finalize,
+                           float* out, float* new_cache, int16_t* pcm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
