@@ -6,6 +6,8 @@ samples to log-mel.  Only the CosyVoice-300M setting is built -- 22 050 Hz, n_ff
 bands over 0 .. 8000 Hz, ``center=False`` -- and every other setting raises ``NotImplementedError`` naming it; audio at
 another rate is resampled first, by the caller: ``Resampler`` / ``resample`` run ``cvft_resample`` (csrc/resample.hip), the
 published formula of ``torchaudio.transforms.Resample`` with its defaults (``sinc_kernel``).
+``whisper_log_mel`` and ``kaldi_fbank`` are the two 16 kHz front-ends of the reference's speech tokenizer and speaker
+encoder (``cvft_feat16k``, csrc/feat16k.hip).
 
 ``mel_filterbank`` restates the documented formula of ``librosa.filters.mel`` with its defaults (Slaney scale, Slaney
 area normalisation) in fp64, rounded once to fp32; it is not a copy of librosa's output.
@@ -327,3 +329,197 @@ def resample(wav: torch.Tensor, orig: int, new: int, lengths: Optional[Sequence[
     if not wav.is_cuda:
         raise CvftError("resample needs a ROCm device tensor; there is no CPU fallback")
     return resampler(orig, new, wav.device)(wav, lengths)
+
+
+# ---------------------------------------------------------------------------------
+# the 16 kHz front-ends (cosyvoice/cli/frontend.py:131-152): whisper.log_mel_spectrogram(speech, n_mels=128) for the speech
+# tokenizer, torchaudio's kaldi.fbank(speech, num_mel_bins=80, dither=0, sample_frequency=16000) for the speaker encoder
+# ---------------------------------------------------------------------------------
+FRONTEND_RATE = 16000
+FRONT_FRAME, FRONT_HOP, FRONT_TILE = 400, 160, 64          # CVFT_FEAT16K_FRAME / _HOP / _TILE (include/cvft.h)
+FRONT_STEPS = FRONT_FRAME // 16
+KIND_WHISPER, KIND_FBANK = 0, 1                            # CVFT_FEAT16K_WHISPER / _FBANK
+WHISPER_MELS, WHISPER_BINS, WHISPER_CHUNKS = 128, 201, 13
+WHISPER_MIN_SAMPLES, WHISPER_MAX_SAMPLES = 201, 30 * FRONTEND_RATE      # reflect padding; the reference's 30 s assertion
+FBANK_MELS, FBANK_NFFT, FBANK_BINS, FBANK_CHUNKS = 80, 512, 257, 16
+FBANK_MIN_SAMPLES = FRONT_FRAME
+FBANK_LOW_HZ, FBANK_PREEMPH, FBANK_EPS = 20.0, 0.97, 1.1920929e-07
+
+
+def whisper_frames(length: int) -> int:
+    """frames of the whisper log-mel: the STFT of the reflect-padded row has length // 160 + 1, the last is dropped."""
+    return int(length) // FRONT_HOP
+
+
+def fbank_frames(length: int) -> int:
+    """frames of the kaldi fbank (snip_edges): 1 + (length - 400) // 160."""
+    return 1 + (int(length) - FRONT_FRAME) // FRONT_HOP
+
+
+def whisper_mel_banks() -> np.ndarray:
+    """[128, 201] fp32: the Slaney bank of mel_filterbank at 16 kHz / 400 / 128 bands / 0 .. 8000 Hz -- the formula whisper's
+    stored asset was made with, restated; not a copy of that asset."""
+    return mel_filterbank(FRONTEND_RATE, FRONT_FRAME, WHISPER_MELS, 0.0, 8000.0)
+
+
+def kaldi_mel_banks() -> np.ndarray:
+    """[80, 257] fp32: torchaudio's get_mel_banks(80, 512, 16000, 20, 0, ...) restated in fp64 and rounded once.
+    mel(f) = 1127 ln(1 + f / 700); 82 edges equally spaced from mel(20) to mel(8000); band b's weight at bin i < 256
+    (f = 31.25 i) is max(0, min((m - left) / (center - left), (right - m) / (right - center))); no area normalisation;
+    column 256 is zero."""
+    mel = lambda f: 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)                   # noqa: E731
+    edges = np.linspace(float(mel(FBANK_LOW_HZ)), float(mel(FRONTEND_RATE / 2.0)), FBANK_MELS + 2)
+    left, center, right = edges[:-2, None], edges[1:-1, None], edges[2:, None]
+    m = mel(FRONTEND_RATE / FBANK_NFFT * np.arange(FBANK_NFFT // 2))[None, :]
+    w = np.zeros((FBANK_MELS, FBANK_BINS), dtype=np.float64)
+    w[:, :FBANK_NFFT // 2] = np.maximum(0.0, np.minimum((m - left) / (center - left), (right - m) / (right - center)))
+    return w.astype(np.float32)
+
+
+def whisper_dft() -> Tuple[np.ndarray, np.ndarray]:
+    """(cos, sin) fp64 [201, 400]: hann[n] * cos | sin(2 pi (n k mod 400) / 400) with the periodic Hann window."""
+    n = np.arange(FRONT_FRAME)
+    k = np.arange(WHISPER_BINS).reshape(-1, 1)
+    hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / FRONT_FRAME)
+    ang = 2.0 * np.pi * ((n * k) % FRONT_FRAME) / FRONT_FRAME
+    return hann * np.cos(ang), hann * np.sin(ang)
+
+
+def fbank_dft() -> Tuple[np.ndarray, np.ndarray]:
+    """(cos, sin) fp64 [257, 400]: the 512-point DFT of the zero-padded frame after mean removal, pre-emphasis and the Povey
+    window, as one matrix on the raw frame: D . diag(w) . P . (I - 11^T / 400).  All three steps are linear in the frame,
+    so the cancellations (the frame's mean, x[n] - 0.97 x[n - 1]) happen here in fp64 rather than in fp32 on the samples."""
+    n = np.arange(FRONT_FRAME)
+    k = np.arange(FBANK_BINS).reshape(-1, 1)
+    povey = (0.5 - 0.5 * np.cos(2.0 * np.pi * n / (FRONT_FRAME - 1))) ** 0.85
+    pre = np.eye(FRONT_FRAME) - FBANK_PREEMPH * np.eye(FRONT_FRAME, k=-1)
+    pre[0, 0] -= FBANK_PREEMPH                                         # y[0] = x[0] - 0.97 x[0]
+    lin = povey[:, None] * (pre @ (np.eye(FRONT_FRAME) - 1.0 / FRONT_FRAME))
+    ang = 2.0 * np.pi * ((n * k) % FBANK_NFFT) / FBANK_NFFT
+    return np.cos(ang) @ lin, np.sin(ang) @ lin
+
+
+def pack_frame_dft(cos: np.ndarray, sin: np.ndarray, nchunks: int, live: Optional[np.ndarray] = None) -> np.ndarray:
+    """the DFT operand of cvft_feat16k (include/cvft.h): dense fp64 [bins, 400] tables rounded once,
+    [chunk][step][cos | sin][lane][e] with k = 16 c + (l & 15), n = 16 s + 4 (l >> 4) + e; zero for bins past the table
+    and for bins where `live` (bool [bins]) is false."""
+    nbin = cos.shape[0]
+    full = np.zeros((2, 16 * nchunks, FRONT_FRAME), dtype=np.float32)
+    keep = np.ones(nbin, dtype=bool) if live is None else np.asarray(live, dtype=bool)
+    m = min(nbin, 16 * nchunks)
+    full[0, :m] = np.where(keep[:m, None], cos[:m], 0.0)
+    full[1, :m] = np.where(keep[:m, None], sin[:m], 0.0)
+    c = np.arange(nchunks).reshape(-1, 1, 1, 1, 1)
+    s = np.arange(FRONT_STEPS).reshape(1, -1, 1, 1, 1)
+    cs = np.arange(2).reshape(1, 1, -1, 1, 1)
+    lane = np.arange(64).reshape(1, 1, 1, -1, 1)
+    e = np.arange(4).reshape(1, 1, 1, 1, -1)
+    return np.ascontiguousarray(full[cs, 16 * c + (lane & 15), 16 * s + 4 * (lane >> 4) + e])   # [nchunks, 25, 2, 64, 4]
+
+
+def _rows(wav: torch.Tensor, lengths, lo: int, hi: Optional[int], what: str):
+    if wav.dim() == 1:
+        wav = wav.unsqueeze(0)
+    if wav.dim() != 2:
+        raise ValueError(f"wav must be [B, L] or [L], got {tuple(wav.shape)}")
+    B, Lmax = wav.shape
+    lens = [Lmax] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+    if len(lens) != B:
+        raise ValueError(f"{len(lens)} lengths for {B} rows")
+    top = Lmax if hi is None else min(Lmax, hi)
+    for i, n in enumerate(lens):
+        if n < lo or n > top:
+            raise ValueError(f"row {i}: {n} samples outside [{lo}, {top}] ({what})")
+    return wav, lens
+
+
+class WhisperMelExtractor:
+    """The speech tokenizer's input.  Holds the packed tables on `device` once; ``__call__`` is two kernel launches."""
+
+    def __init__(self, device: Union[str, torch.device] = 'cuda'):
+        self.device = torch.device(device)
+        self.basis = whisper_mel_banks()
+        self.nchunks = WHISPER_CHUNKS
+        self.dft_tab = torch.from_numpy(pack_frame_dft(*whisper_dft(), self.nchunks)).to(self.device)
+        self.basis_tab = torch.from_numpy(pack_basis(self.basis, self.nchunks)).to(self.device)
+
+    @staticmethod
+    def rows(wav: torch.Tensor, lengths):
+        """-> (wav [B, Lmax], lengths); ValueError naming the row whose length is outside [201, 480000]."""
+        return _rows(wav, lengths, WHISPER_MIN_SAMPLES, WHISPER_MAX_SAMPLES,
+                     "reflect padding reads 200 samples past each end; the tokenizer takes at most 30 s")
+
+    def __call__(self, wav: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """wav [B, Lmax] (or [L]) fp32 at 16 kHz on the device -> [B, 128, Tmax]: row b has lengths[b] // 160 frames of
+        (max(log10(max(mel, 1e-10)), rowmax - 8) + 4) / 4 and 0 after them."""
+        from .hipops import functional as HF
+        wav, lens = self.rows(wav, lengths)
+        return HF.feat16k(KIND_WHISPER, wav, lens, self.dft_tab, self.basis_tab, self.nchunks, whisper_frames(max(lens)))
+
+
+class FbankExtractor:
+    """The speaker encoder's input.  Holds the packed tables on `device` once; ``__call__`` is two kernel launches (one
+    with ``cmn=False``)."""
+
+    def __init__(self, device: Union[str, torch.device] = 'cuda'):
+        self.device = torch.device(device)
+        self.basis = kaldi_mel_banks()
+        self.nchunks = FBANK_CHUNKS
+        live = self.basis.any(axis=0)                                       # bins 1 .. 255
+        self.dft_tab = torch.from_numpy(pack_frame_dft(*fbank_dft(), self.nchunks, live)).to(self.device)
+        self.basis_tab = torch.from_numpy(pack_basis(self.basis, self.nchunks)).to(self.device)
+
+    @staticmethod
+    def rows(wav: torch.Tensor, lengths):
+        """-> (wav [B, Lmax], lengths); ValueError naming the row that is shorter than one frame of 400 samples."""
+        return _rows(wav, lengths, FBANK_MIN_SAMPLES, None, "a frame is 400 samples, snip_edges")
+
+    def __call__(self, wav: torch.Tensor, lengths: Optional[Sequence[int]] = None, cmn: bool = True) -> torch.Tensor:
+        """wav [B, Lmax] (or [L]) fp32 in [-1, 1] at 16 kHz on the device -> [B, Mmax, 80]: row b has
+        1 + (lengths[b] - 400) // 160 frames of log(max(energy, 2^-23)), minus each band's mean over them with `cmn`, and
+        0 after them."""
+        from .hipops import functional as HF
+        wav, lens = self.rows(wav, lengths)
+        return HF.feat16k(KIND_FBANK, wav, lens, self.dft_tab, self.basis_tab, self.nchunks, fbank_frames(max(lens)),
+                          finish=bool(cmn))
+
+
+_FRONT_EXTRACTORS = {}
+
+
+def _front_extractor(cls, device):
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    if (cls, device) not in _FRONT_EXTRACTORS:
+        _FRONT_EXTRACTORS[(cls, device)] = cls(device)
+    return _FRONT_EXTRACTORS[(cls, device)]
+
+
+def whisper_extractor(device) -> WhisperMelExtractor:
+    """one WhisperMelExtractor per device, built on first use."""
+    return _front_extractor(WhisperMelExtractor, device)
+
+
+def fbank_extractor(device) -> FbankExtractor:
+    """one FbankExtractor per device, built on first use."""
+    return _front_extractor(FbankExtractor, device)
+
+
+def whisper_log_mel(wav: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """whisper.log_mel_spectrogram(wav, n_mels=128) per row: wav [B, L] or [L] at 16 kHz on the device -> [B, 128, Tmax]."""
+    from .hipops.binding import CvftError
+    WhisperMelExtractor.rows(wav, lengths)                                  # length errors come first, device or not
+    if not wav.is_cuda:
+        raise CvftError("whisper_log_mel needs a ROCm device tensor; there is no CPU fallback")
+    return whisper_extractor(wav.device)(wav, lengths)
+
+
+def kaldi_fbank(wav: torch.Tensor, lengths: Optional[Sequence[int]] = None, cmn: bool = True) -> torch.Tensor:
+    """kaldi.fbank(wav, num_mel_bins=80, dither=0, sample_frequency=16000) per row, minus its mean over the row's frames
+    with `cmn`: wav [B, L] or [L] at 16 kHz on the device -> [B, Mmax, 80]."""
+    from .hipops.binding import CvftError
+    FbankExtractor.rows(wav, lengths)
+    if not wav.is_cuda:
+        raise CvftError("kaldi_fbank needs a ROCm device tensor; there is no CPU fallback")
+    return fbank_extractor(wav.device)(wav, lengths, cmn)

@@ -198,6 +198,8 @@ SIGNATURES = {
     "cvft_hift_istft": [_i, _i, _p, _i, _f, _p, _p, _p],
     "cvft_melspec": [_i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p, _p],
     "cvft_resample": [_i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p],
+    "cvft_feat16k": [_i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p],
+    "cvft_feat16k_finish": [_i, _i, _i, _p, _i, _p, _p, _p],
     "cvft_stream_mel_stitch": [_i, _i, _i, _p, _i, _i, _f, _f, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p],
     "cvft_stream_wav_stitch": [_i, _p, _i, _p, _p, _i, _p, _p, _p, _p],
 }

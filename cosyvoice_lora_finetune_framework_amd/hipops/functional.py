@@ -2458,6 +2458,43 @@ def resample(wav: torch.Tensor, lengths: Sequence[int], o: int, n: int, width: i
     return out
 
 
+def feat16k(kind: int, wav: torch.Tensor, lengths: Sequence[int], dft_tab: torch.Tensor, basis_tab: torch.Tensor,
+            nchunks: int, Tmax: int, finish: bool = True) -> torch.Tensor:
+    """cvft_feat16k (+ cvft_feat16k_finish with `finish`): wav [B, Lmax] fp32 at 16 kHz with per-row sample counts ->
+    kind 0: the whisper log-mel [B, 128, Tmax]; kind 1: the kaldi fbank [B, Tmax, 80], its per-band mean over the row's
+    frames subtracted with `finish`.  The tables come from audio.pack_frame_dft / audio.pack_basis
+    (audio.WhisperMelExtractor / audio.FbankExtractor hold them).  kind 0 always takes both launches."""
+    if kind not in (0, 1):
+        raise ValueError(f"kind {kind}: 0 is the whisper log-mel, 1 the kaldi fbank")
+    bands, need = (128, 201) if kind == 0 else (80, 400)
+    for name, t in (("wav", wav), ("dft_tab", dft_tab), ("basis_tab", basis_tab)):
+        if not t.is_cuda:
+            raise cb.CvftError(f"libcvft ops need ROCm device tensors ({name} is not); there is no CPU fallback")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be fp32, got {t.dtype}")
+    if wav.dim() != 2:
+        raise ValueError(f"wav must be [B, Lmax], got {tuple(wav.shape)}")
+    B, Lmax = wav.shape
+    lens = [int(v) for v in lengths]
+    if len(lens) != B or any(v < need or v > Lmax for v in lens):
+        raise ValueError(f"lengths {lens} for {B} rows of {Lmax} samples (this feature needs at least {need} per row)")
+    if dft_tab.numel() != nchunks * 25 * 2 * 64 * 4 or basis_tab.numel() != nchunks * (bands // 16) * 64 * 4:
+        raise ValueError(f"tables of {dft_tab.numel()} and {basis_tab.numel()} floats for {nchunks} chunks and {bands} bands")
+    if Tmax < 1:
+        raise ValueError(f"Tmax={Tmax}")
+    wav, dft_tab, basis_tab = _c(wav), _c(dft_tab), _c(basis_tab)
+    ln = torch.tensor(lens, dtype=torch.int32).to(wav.device)
+    out = torch.empty((B, bands, Tmax) if kind == 0 else (B, Tmax, bands), dtype=torch.float32, device=wav.device)
+    finish = bool(finish) or kind == 0
+    ntiles = (Tmax + 63) // 64
+    work = torch.empty((B, ntiles, 1 if kind == 0 else bands), dtype=torch.float32, device=wav.device) if finish else None
+    check(lib().cvft_feat16k(kind, B, Lmax, Lmax, ptr(wav), ptr(ln), ptr(dft_tab), ptr(basis_tab), nchunks, Tmax, ptr(out),
+                             ptr(work), stream()), "cvft_feat16k")
+    if finish:
+        check(lib().cvft_feat16k_finish(kind, B, Lmax, ptr(ln), Tmax, ptr(work), ptr(out), stream()), "cvft_feat16k_finish")
+    return out
+
+
 def stream_mel_stitch(x: torch.Tensor, trim: int, ov: int, window: Optional[torch.Tensor], prev: Optional[torch.Tensor] = None,
                       cache: Optional[torch.Tensor] = None, finalize: bool = False, scale_shift=None, cache_len: int = 0):
     """cvft_stream_mel_stitch: the chunk's Flow output x [C, Tn] fp32 -> (vocoder input [C, mc + Tn - trim - (0 if finalize

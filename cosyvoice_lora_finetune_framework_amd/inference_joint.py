@@ -7,6 +7,7 @@ without the text front-end.
         [--top-p 0.8 --top-k 25 --win-size 10 --tau-r 0.1] [--llm-config '{...}' --flow-config '{...}'] [--noise z.npy]
         [--hift hift.pt --wav out.wav [--wav-rate 22050] [--hift-dtype fp32] [--hift-seed 0]]
         [--prompt-wav p.wav --prompt-tokens 5,9,.. --prompt-text-tokens 3,4,.. --embedding e.npy]
+        [--speech-tokenizer speech_tokenizer_v1.onnx] [--campplus campplus.onnx]
         [--stream [--token-hop 100]]
 
 ``--llm`` / ``--flow`` are the merged state_dicts ``merge_joint_weights.py`` writes; ``--text-tokens`` is a comma-separated
@@ -22,6 +23,10 @@ of other dimensions than CosyVoice-300M; ``--noise`` pins the Flow's initial noi
 Flow's prompt mel on the GPU (``audio.MelExtractor``);
 ``--prompt-tokens`` / ``--prompt-text-tokens`` are the prompt's speech and text token ids (they come from the reference's
 tokenizers, which are not rebuilt here) and ``--embedding`` its speaker embedding.  Without them the prompt is empty.
+``--speech-tokenizer`` / ``--campplus`` (the reference's two ONNX files, run by ``onnxruntime`` on the CPU) make
+``--prompt-wav`` alone enough: the prompt is resampled to 16 kHz on the GPU, its Whisper log-mel and Kaldi fbank are formed
+there (``frontend16k.SpeechFrontend``) and the models turn them into the prompt's speech tokens and the speaker embedding.
+An explicit ``--prompt-tokens`` or ``--embedding`` still wins.
 ``--stream`` (needs ``--hift``) synthesises chunk by chunk while the LLM keeps decoding (``streaming.StreamingSynthesizer``,
 the reference's ``tts(stream=True)``): each chunk is appended to ``--wav`` as it arrives, the time to the first chunk and
 the total time are printed and no mel file is written.  ``--token-hop`` is the number of new speech tokens per chunk
@@ -48,14 +53,18 @@ from .config import MEL_MEAN, MEL_STD
 def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] = None,
                noise: Optional[torch.Tensor] = None, *, prompt_wav: Optional[torch.Tensor] = None,
                prompt_speech_token=None, prompt_text=None, embedding: Optional[torch.Tensor] = None,
-               prompt_rate: Optional[int] = None) -> Tuple[List[int], torch.Tensor]:
+               prompt_rate: Optional[int] = None, frontend=None) -> Tuple[List[int], torch.Tensor]:
     """-> (speech tokens, de-normalised mel (1, 80, T) fp32).  `seed` pins the LLM's sampler, `noise` the Flow's
     initial z.  Zero-shot prompting: `prompt_wav` (samples at 22 050 Hz, or at `prompt_rate` Hz: then it is resampled to
     22 050 Hz first, audio.Resampler) becomes the Flow's `prompt_feat` -- its log-mel
     (audio.MelExtractor), normalised with MEL_MEAN / MEL_STD as the reference's patched flow inference does for a
     non-empty prompt --, `prompt_speech_token` goes to both models, `prompt_text` to the LLM, `embedding` (1, 192) to
-    both.  With none of them the prompt is empty and the embedding zero."""
+    both.  With none of them the prompt is empty and the embedding zero.  `frontend` (frontend16k.SpeechFrontend) fills
+    what `prompt_wav` comes without: `prompt_speech_token` from its speech tokenizer, `embedding` from its speaker
+    encoder, both on the prompt resampled to 16 kHz; a value passed explicitly wins."""
     dev = llm.llm_decoder.weight.device
+    if frontend is not None and prompt_wav is not None:
+        prompt_speech_token, embedding = prompt_from_wav(frontend, prompt_wav, prompt_rate, dev, prompt_speech_token, embedding)
     text = torch.as_tensor(text_tokens, dtype=torch.long).reshape(1, -1).to(dev)
     z = torch.zeros(1, 0, dtype=torch.long, device=dev)
     zero = torch.tensor([0])
@@ -80,6 +89,23 @@ def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] =
     if speed != 1.0:
         mel = F.interpolate(mel, size=int(mel.shape[2] / speed), mode='linear')
     return tokens, mel
+
+
+def prompt_from_wav(frontend, prompt_wav: torch.Tensor, prompt_rate: Optional[int], dev, prompt_speech_token=None,
+                    embedding: Optional[torch.Tensor] = None):
+    """-> (prompt_speech_token, embedding): whichever is None and has a model in `frontend` is computed from `prompt_wav`
+    (at `prompt_rate` Hz, default 22 050) resampled to 16 kHz on `dev`."""
+    from .audio import FRONTEND_RATE, SAMPLE_RATE, resample
+    want_tok = prompt_speech_token is None and frontend.speech_tokenizer is not None
+    want_emb = embedding is None and frontend.speaker_encoder is not None
+    if want_tok or want_emb:
+        w16, _ = resample(prompt_wav.float().reshape(1, -1).to(dev), SAMPLE_RATE if prompt_rate is None else int(prompt_rate),
+                          FRONTEND_RATE)
+        if want_tok:
+            prompt_speech_token = frontend.tokens(w16)[0]
+        if want_emb:
+            embedding = frontend.embeddings(w16)
+    return prompt_speech_token, embedding
 
 
 @torch.no_grad()
@@ -131,6 +157,8 @@ def main(argv=None):
     ap.add_argument('--prompt-tokens', default=None, help='the prompt\'s speech token ids (comma-separated or .npy)')
     ap.add_argument('--prompt-text-tokens', default=None, help='the prompt\'s text token ids (comma-separated or .npy)')
     ap.add_argument('--embedding', default=None, help='.npy of the speaker embedding (192 floats); default zero')
+    ap.add_argument('--speech-tokenizer', default=None, help='the speech tokenizer\'s .onnx: --prompt-wav yields the prompt tokens')
+    ap.add_argument('--campplus', default=None, help='the speaker encoder\'s .onnx: --prompt-wav yields the embedding')
     ap.add_argument('--hift', default=None, help='HiFT generator state_dict (hift.pt): also vocode the mel')
     ap.add_argument('--wav', default='out.wav', help='with --hift: the waveform, 16-bit PCM at --wav-rate')
     ap.add_argument('--wav-rate', type=int, default=22050, help='rate of --wav; other than 22050: resampled on the GPU')
@@ -168,6 +196,15 @@ def main(argv=None):
         prompt['prompt_text'] = _text_tokens(a.prompt_text_tokens)
     if a.embedding:
         prompt['embedding'] = torch.from_numpy(np.load(a.embedding)).float()
+    if (a.speech_tokenizer or a.campplus) and a.prompt_wav:
+        from .frontend16k import SpeechFrontend
+        fe = SpeechFrontend.from_onnx(a.speech_tokenizer, a.campplus, dev)
+        tok, emb = prompt_from_wav(fe, prompt['prompt_wav'], prompt['prompt_rate'], dev, prompt.get('prompt_speech_token'),
+                                   prompt.get('embedding'))
+        if tok is not None:
+            prompt['prompt_speech_token'] = tok
+        if emb is not None:
+            prompt['embedding'] = emb
     if a.stream:
         return _stream_main(a, llm, flow, dev, prompt)
     tokens, mel = synthesize(llm, flow, _text_tokens(a.text_tokens), a.speed, a.seed, noise=noise, **prompt)

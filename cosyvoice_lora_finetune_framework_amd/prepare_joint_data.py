@@ -2,7 +2,7 @@
 the reference's ``prepare_joint_data.py``.
 
     python -m cosyvoice_lora_finetune_framework_amd.prepare_joint_data --manifest m.jsonl --output-dir D \\
-        [--samples-per-file 100] [--batch 16]
+        [--samples-per-file 100] [--batch 16] [--speech-tokenizer speech_tokenizer_v1.onnx] [--campplus campplus.onnx]
 
 Each manifest line is a JSON object with ``utt``, ``wav`` (16-bit PCM at 22 050 Hz; a relative path is taken from the
 manifest's directory), ``text``, ``text_token``, ``speech_token`` (id lists) and ``utt_embedding`` (192 floats).  The
@@ -13,6 +13,12 @@ Files that are not at 22 050 Hz are resampled to it on the GPU first (``audio.Re
 torchaudio (prepare_joint_data.py:172-174).  ``--resampled-dir`` with ``--resampled-rate`` also writes every kept
 utterance resampled to that rate as ``<utt>.wav`` (16-bit PCM): 16 000 Hz is what the reference's speech tokenizer and
 speaker encoder take, so their inputs need no other tool.
+
+With ``--speech-tokenizer`` / ``--campplus`` (the reference's two ONNX files; ``onnxruntime`` runs them on the CPU) the
+matching manifest key becomes optional: an entry without ``speech_token`` / ``utt_embedding`` gets it computed, per batch,
+from the 16 kHz resample of the audio already on the device -- the Whisper log-mel and the Kaldi fbank are formed on the GPU
+(``audio.whisper_log_mel`` / ``audio.kaldi_fbank``; ``frontend16k.SpeechFrontend``).  A value the manifest carries wins.
+Without the two options nothing changes, the error for a missing key included.
 
 Like the reference (prepare_joint_data.py:252-256) utterances shorter than 0.5 s or longer than 30 s are dropped.
 Output: ``data_%06d.parquet`` with the reference's columns -- utt, text, text_token, speech_token, speech_feat
@@ -35,8 +41,9 @@ REQUIRED = ("utt", "wav", "text", "text_token", "speech_token", "utt_embedding")
 COLUMNS = ("utt", "text", "text_token", "speech_token", "speech_feat", "speech_feat_shape", "utt_embedding", "spk_embedding")
 
 
-def read_manifest(path: str) -> List[Dict[str, Any]]:
-    """JSON lines -> entries with every REQUIRED key; `wav` resolved against the manifest's directory."""
+def read_manifest(path: str, computed: Tuple[str, ...] = ()) -> List[Dict[str, Any]]:
+    """JSON lines -> entries with every REQUIRED key; `wav` resolved against the manifest's directory.  Keys named in
+    `computed` (speech_token, utt_embedding) may be absent: the caller has a model that fills them."""
     base = os.path.dirname(os.path.abspath(path))
     out = []
     with open(path, "r", encoding="utf-8") as f:
@@ -45,10 +52,10 @@ def read_manifest(path: str) -> List[Dict[str, Any]]:
             if not line:
                 continue
             e = json.loads(line)
-            missing = [k for k in REQUIRED if k not in e]
+            missing = [k for k in REQUIRED if k not in e and k not in computed]
             if missing:
                 raise ValueError(f"{path}:{no}: missing {', '.join(missing)}")
-            if not e["text_token"] or not e["speech_token"]:
+            if not e["text_token"] or ("speech_token" in e and not e["speech_token"]):
                 raise ValueError(f"{path}:{no}: {e['utt']}: empty token list")
             e = dict(e)
             if not os.path.isabs(e["wav"]):
@@ -94,10 +101,11 @@ def _batches(wavs: List[torch.Tensor], rates: List[int], batch: int):
 
 
 def extract_feats(entries: List[Dict[str, Any]], device, batch: int = 16, resampled_dir: Optional[str] = None,
-                  resampled_rate: Optional[int] = None) -> List[torch.Tensor]:
+                  resampled_rate: Optional[int] = None, frontend=None) -> List[torch.Tensor]:
     """speech_feat [T, 80] (CPU fp32) per entry, in the entries' order.  Files at another rate than 22 050 Hz are
     resampled to it on the GPU, batched per source rate; with `resampled_dir` every entry is also written there as
-    <utt>.wav at `resampled_rate`."""
+    <utt>.wav at `resampled_rate`.  With `frontend` (frontend16k.SpeechFrontend) the entries that lack speech_token /
+    utt_embedding get them, in place, from the batch's 16 kHz resample and the frontend's models."""
     ext = A.extractor(device)
     wavs, rates = [], []
     for e in entries:
@@ -117,7 +125,27 @@ def extract_feats(entries: List[Dict[str, Any]], device, batch: int = 16, resamp
             z = z.cpu()
             for r, i in enumerate(idx):
                 write_wav(os.path.join(resampled_dir, f"{entries[i]['utt']}.wav"), z[r, :zlens[r]], int(resampled_rate))
+        if frontend is not None:
+            _fill_from_models(entries, idx, frontend, x, rate, lens)
     return feats
+
+
+def _fill_from_models(entries, idx, frontend, x: torch.Tensor, rate: int, lens: List[int]) -> None:
+    """speech_token / utt_embedding of the batch's entries that lack them: one feature call per model over those rows."""
+    for key, have in (("speech_token", frontend.speech_tokenizer), ("utt_embedding", frontend.speaker_encoder)):
+        rows = [r for r, i in enumerate(idx) if key not in entries[i]]
+        if have is None or not rows:
+            continue
+        sub = x if len(rows) == len(idx) else x[rows, :max(lens[r] for r in rows)].contiguous()
+        z, zlens = A.resample(sub, rate, A.FRONTEND_RATE, [lens[r] for r in rows])
+        if key == "speech_token":
+            for r, ids in zip(rows, frontend.tokens(z, zlens)):
+                if not ids:
+                    raise ValueError(f"{entries[idx[r]]['utt']}: the speech tokenizer returned no tokens")
+                entries[idx[r]][key] = ids
+        else:
+            for r, emb in zip(rows, frontend.embeddings(z, zlens)):
+                entries[idx[r]][key] = emb.tolist()
 
 
 def make_row(e: Dict[str, Any], feat: torch.Tensor) -> Dict[str, Any]:
@@ -136,20 +164,28 @@ def write_shard(rows: List[Dict[str, Any]], output_dir: str, index: int) -> str:
 
 
 def prepare(manifest: str, output_dir: str, samples_per_file: int = 100, batch: int = 16, device="cuda",
-            verbose: bool = True, resampled_dir: Optional[str] = None, resampled_rate: Optional[int] = None) -> List[str]:
-    """-> the shard paths written (also listed in output_dir/data.list)."""
+            verbose: bool = True, resampled_dir: Optional[str] = None, resampled_rate: Optional[int] = None,
+            speech_tokenizer=None, speaker_encoder=None) -> List[str]:
+    """-> the shard paths written (also listed in output_dir/data.list).  `speech_tokenizer` / `speaker_encoder`: the
+    callables of frontend16k.SpeechFrontend; with one given, entries may lack speech_token / utt_embedding."""
     if (resampled_dir is None) != (resampled_rate is None):
         raise ValueError("--resampled-dir and --resampled-rate go together")
     os.makedirs(output_dir, exist_ok=True)
     if resampled_dir is not None:
         os.makedirs(resampled_dir, exist_ok=True)
-    entries = filter_entries(read_manifest(manifest), verbose)
+    frontend = None
+    if speech_tokenizer is not None or speaker_encoder is not None:
+        from .frontend16k import SpeechFrontend
+        frontend = SpeechFrontend(device, speech_tokenizer, speaker_encoder)
+    computed = tuple(k for k, m in (("speech_token", speech_tokenizer), ("utt_embedding", speaker_encoder)) if m is not None)
+    entries = filter_entries(read_manifest(manifest, computed), verbose)
     if not entries:
         raise RuntimeError(f"{manifest}: no utterance left after the duration filter")
     shards = []
     for i0 in range(0, len(entries), samples_per_file):
         part = entries[i0:i0 + samples_per_file]
-        rows = [make_row(e, f) for e, f in zip(part, extract_feats(part, device, batch, resampled_dir, resampled_rate))]
+        feats = extract_feats(part, device, batch, resampled_dir, resampled_rate, frontend)
+        rows = [make_row(e, f) for e, f in zip(part, feats)]
         shards.append(write_shard(rows, output_dir, len(shards)))
         if verbose:
             print(f"  wrote {shards[-1]} ({len(rows)} utterances)")
@@ -167,9 +203,16 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--resampled-dir", default=None, help="also write every kept utterance here as <utt>.wav at --resampled-rate")
     ap.add_argument("--resampled-rate", type=int, default=None, help="rate of the files in --resampled-dir, e.g. 16000")
+    ap.add_argument("--speech-tokenizer", default=None, help="the speech tokenizer's .onnx: speech_token becomes optional")
+    ap.add_argument("--campplus", default=None, help="the speaker encoder's .onnx: utt_embedding becomes optional")
     a = ap.parse_args(argv)
+    models = {}
+    if a.speech_tokenizer or a.campplus:
+        from .frontend16k import SpeechFrontend
+        fe = SpeechFrontend.from_onnx(a.speech_tokenizer, a.campplus)
+        models = dict(speech_tokenizer=fe.speech_tokenizer, speaker_encoder=fe.speaker_encoder)
     shards = prepare(a.manifest, a.output_dir, a.samples_per_file, a.batch, resampled_dir=a.resampled_dir,
-                     resampled_rate=a.resampled_rate)
+                     resampled_rate=a.resampled_rate, **models)
     print(f"{len(shards)} shard(s) -> {os.path.join(a.output_dir, 'data.list')}")
 
 

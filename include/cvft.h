@@ -666,6 +666,50 @@ int cvft_resample(int B, int Lmax, int ldw, const float* wav, const int* len, in
                   const int* first, const float* taps, int Mmax, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * 16 kHz front-ends (cosyvoice/cli/frontend.py:131-152: what the reference computes with whisper.log_mel_spectrogram(speech,
+ * n_mels=128) for its speech tokenizer and with torchaudio's kaldi.fbank(speech, num_mel_bins=80, dither=0,
+ * sample_frequency=16000) minus the per-band mean for its speaker encoder; feat16k.hip).  Both are frames of
+ * CVFT_FEAT16K_FRAME samples at hop CVFT_FEAT16K_HOP; a workgroup owns CVFT_FEAT16K_TILE consecutive frames of one row.
+ * Two launches per feature, no atomics, bit-identical run to run and row by row.
+ *
+ * cvft_feat16k: wav [B][ldw] fp32 (row b holds len[b] <= Lmax samples; len == NULL: every row holds Lmax).
+ *   kind == CVFT_FEAT16K_WHISPER: out [B][128][Tmax].  Row b has T_b = min(len[b] / 160, Tmax) frames (none when
+ *     len[b] < 201) and 0 after them.  Frame t is padded samples [160 t, 160 t + 400), padded index p -> sample s = p - 200,
+ *     s < 0: -s, s >= len: 2 (len - 1) - s; times the periodic Hann window; 400-point real DFT, bins 0 .. 200;
+ *     power = re^2 + im^2; mel = basis . power; out = log10(max(mel, 1e-10)) (exactly -10 at the floor).
+ *     work [B][ceil(Tmax / 64)] receives each workgroup's maximum over its valid frames (-inf when it has none).
+ *   kind == CVFT_FEAT16K_FBANK: out [B][Tmax][80].  Row b has T_b = min(1 + (len[b] - 400) / 160, Tmax) frames (none when
+ *     len[b] < 400) and 0 after them.  Frame t is samples [160 t, 160 t + 400): minus the frame's mean, pre-emphasis
+ *     y[n] = x[n] - 0.97 x[max(n - 1, 0)], Povey window, zero-padded to 512, real DFT, bins 0 .. 255 -- all of it linear in
+ *     the frame and folded into dft_tab; power; energy = basis . power; out = log(max(energy, 2^-23)) (exactly
+ *     fp32(log(2^-23)) at the floor).  work [B][ceil(Tmax / 64)][80] receives each workgroup's per-band sums of out over
+ *     its valid frames, added in frame order; work == NULL: not written (no mean subtraction wanted).
+ *   dft_tab: nchunks * 25 * 2 * 64 * 4 floats, [chunk c][step s][cos | sin][lane l][e] = the DFT matrix's entry for bin
+ *   k = 16 c + (l & 15) and sample n = 16 s + 4 (l >> 4) + e.  basis_tab: nchunks * (bands / 16) * 64 * 4 floats,
+ *   [c][band tile m][lane l][i] = basis[16 m + (l & 15)][16 c + 4 (l >> 4) + i].  Both are zero where the bin or band does
+ *   not exist or carries no weight, both 16-byte aligned.  nchunks <= CVFT_FEAT16K_WHISPER_CHUNKS (201 bins) or
+ *   CVFT_FEAT16K_FBANK_CHUNKS (bins 1 .. 255 carry weight).
+ *   (audio.py: pack_frame_dft / whisper_dft / fbank_dft / pack_basis build them.)
+ * cvft_feat16k_finish: the row-wide step, in place on out, with the same B, Lmax, len and Tmax.
+ *   whisper: rowmax = the maximum of the row's workgroup maxima; out = (max(out, rowmax - 8) + 4) / 4 on the valid frames.
+ *   fbank: mean[band] = (the row's workgroup sums added in workgroup order) / T_b; out -= mean on the valid frames.
+ * Refused, with nothing launched: another kind; B outside [1, 65535]; Lmax below 201 (whisper) / 400 (fbank) or above
+ *   2^30; ldw < Lmax; Tmax outside [1, 2^23]; nchunks outside its range; a null or misaligned pointer.
+ * ------------------------------------------------------------------------------- */
+#define CVFT_FEAT16K_WHISPER 0
+#define CVFT_FEAT16K_FBANK 1
+#define CVFT_FEAT16K_FRAME 400
+#define CVFT_FEAT16K_HOP 160
+#define CVFT_FEAT16K_TILE 64
+#define CVFT_FEAT16K_WHISPER_BANDS 128
+#define CVFT_FEAT16K_FBANK_BANDS 80
+#define CVFT_FEAT16K_WHISPER_CHUNKS 13
+#define CVFT_FEAT16K_FBANK_CHUNKS 16
+int cvft_feat16k(int kind, int B, int Lmax, int ldw, const float* wav, const int* len, const float* dft_tab,
+                 const float* basis_tab, int nchunks, int Tmax, float* out, float* work, void* stream);
+int cvft_feat16k_finish(int kind, int B, int Lmax, const int* len, int Tmax, const float* work, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Streaming synthesis (cosyvoice/cli/model.py CosyVoiceModel.token2wav; stream.hip): what joins consecutive chunks, each
  * side in one elementwise launch.  No LDS, no atomics, one writer per output element, bit-identical run to run.
  * A fade is in * w[j] + out * w[n + j] over a window w of 2 n fp32 values, summed in fp64 and rounded once to fp32 (the
