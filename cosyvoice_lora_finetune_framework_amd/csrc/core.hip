@@ -19,7 +19,7 @@ extern "C" void cvft_set_kernel_label(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cvft_gemm_last_kernel(void) { return g_kernel; }
-extern "C" int cvft_version(void) { return 102; }
+extern "C" int cvft_version(void) { return 103; }
 
 // Execution hint (performance only, never results): how many independent kernel chains the caller runs concurrently on
 // separate streams.  Kernels that own a whole CU (one workgroup per CU: the 96x256 GEMM tile) cannot share it with another

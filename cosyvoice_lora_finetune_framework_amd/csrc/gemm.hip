@@ -15,7 +15,9 @@
 // loads past the last tile are issued anyway and return zeros).  !AL: guarded element loads.
 // Epilogue: accumulators -> LDS (fp32) -> 16-byte coalesced row segments with the whole
 // bias/act/act'/residual/mask chain applied on the vectors.
-template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU>
+// X: 0 plain; 1 two-output launch (GP::C2: column tiles >= N1 run the centre tap only and write C2 -- a k = 3 convolution and the
+// 1x1 convolution of the same masked input in one launch).  Only on the aligned, unfused 64x64 instantiation (gemm_plan_pair).
+template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU, int X = 0>
 __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(GP<T> p) {
     constexpr int NT = WM * WN * 64;
     constexpr int VEC = 16 / sizeof(T);
@@ -49,6 +51,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(GP<T> p) {
     }
     const int m0 = (bid / tiles_n) * BM;
     const int n0 = (bid % tiles_n) * BN;
+    const bool sc = X == 1 && n0 >= p.N1;          // block-uniform: a tile of the second output
 
     int a_row[A_IT], a_cc[A_IT], a_b[A_IT], a_t[A_IT], a_len[A_IT];
     bool a_ok[A_IT];
@@ -82,7 +85,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(GP<T> p) {
 
     const int nk_main = (p.K + BK - 1) / BK;
     const int nk_lora = (p.R > 0 && !FU) ? (p.R + BK - 1) / BK : 0;
-    const int n_it = p.ntaps * nk_main + nk_lora;
+    const int n_it = (sc ? 1 : p.ntaps) * nk_main + nk_lora;
 
     uint4 ra[D][A_IT], rw[D][W_IT];
     uint4 rl[D];                          // FU: LoRA-A tile chunk (threads < 16*CPR)
@@ -147,7 +150,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(GP<T> p) {
         ld_kt = 0;
     };
     auto gload = [&](uint4 (&ra_)[A_IT], uint4 (&rw_)[W_IT], uint4& rl_) __attribute__((always_inline)) {
-        if (ld_kt == ld_nk) seg_setup(ld_seg + 1);
+        if (ld_kt == ld_nk) seg_setup(sc ? p.ntaps : ld_seg + 1);
         const int k0 = ld_kt * BK;
         const bool lora = ld_seg >= p.ntaps;
         if (FU && AL) {
@@ -227,7 +230,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(GP<T> p) {
         }
     };
 
-    seg_setup(0);
+    seg_setup(sc ? p.ctr : 0);
     // prologue: tiles 0..D-1 in flight, tile 0 staged, its register set refilled with tile D
     static_for<D>([&](auto dc) __attribute__((always_inline)) {
         constexpr int d = decltype(dc)::value;
@@ -305,7 +308,14 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(GP<T> p) {
             for (int r = 0; r < 4; ++r)
                 Cs[(wm * TM + i * 16 + (lane >> 4) * 4 + r) * CLD + wn * TN + j * 16 + (lane & 15)] = acc[i][j][r];
     __syncthreads();
-    gemm_epilogue_store<T, BM, BN, NT>(p, Cs, m0, n0, tid);
+    if (X == 1) {                // each output sees its own columns: [0, N1) of C, [0, N - N1) of C2
+        GP<T> q = p;
+        q.N = sc ? p.N - p.N1 : p.N1;
+        if (sc) { q.C = p.C2; q.ldc = p.ldc2; q.bias = p.bias2; }
+        gemm_epilogue_store<T, BM, BN, NT>(q, Cs, m0, sc ? n0 - p.N1 : n0, tid);
+    } else {
+        gemm_epilogue_store<T, BM, BN, NT>(p, Cs, m0, n0, tid);
+    }
 }
 
 template <typename T>
@@ -326,9 +336,9 @@ const GemmKnobs& gemm_knobs() {
     return knobs;
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU = false>
+template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU = false, int X = 0>
 static int gemm_launch_cfg(const GemmLaunch<T>& l, hipStream_t st, bool enqueue) {
-    auto kern = gemm_kernel<T, BM, BN, WM, WN, D, AL, FU>;
+    auto kern = gemm_kernel<T, BM, BN, WM, WN, D, AL, FU, X>;
     static bool attr_set = false;
     if (!enqueue) return gemm_lds_attr(reinterpret_cast<const void*>(kern), l.lds, attr_set);
     hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.block), l.lds, st, l.p);
@@ -336,7 +346,7 @@ static int gemm_launch_cfg(const GemmLaunch<T>& l, hipStream_t st, bool enqueue)
 }
 
 // the register-staged kernel on tile configuration <BM, BN, WM, WN, D> as the plan's only launch
-template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU = false>
+template <typename T, int BM, int BN, int WM, int WN, int D, bool AL, bool FU = false, int X = 0>
 static int gemm_plan_cfg(const GP<T>& p, GemmPlan<T>& plan) {
     constexpr int VEC = 16 / sizeof(T);
     constexpr int BK = (sizeof(T) == 2) ? 64 : 16;
@@ -345,10 +355,11 @@ static int gemm_plan_cfg(const GP<T>& p, GemmPlan<T>& plan) {
     const size_t cs = (size_t)BM * (BN + 4) * sizeof(float);
     GemmLaunch<T>& l = plan.l[0];
     plan.n = 1;
-    l.fn = gemm_launch_cfg<T, BM, BN, WM, WN, D, AL, FU>;
+    l.fn = gemm_launch_cfg<T, BM, BN, WM, WN, D, AL, FU, X>;
     l.p = p; l.lds = ring > cs ? ring : cs; l.block = WM * WN * 64;
     l.grid = (unsigned)((long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN));
-    snprintf(l.label, sizeof(l.label), "gemm_kernel<%s,%d,%d,%d,%d>%s", sizeof(T) == 2 ? "bf16" : "f32", BM, BN, WM, WN, FU ? ",fusedU" : "");
+    snprintf(l.label, sizeof(l.label), "gemm_kernel<%s,%d,%d,%d,%d>%s", sizeof(T) == 2 ? "bf16" : "f32", BM, BN, WM, WN,
+             FU ? ",fusedU" : X == 1 ? ",two_out" : "");
     return 0;
 }
 
@@ -362,6 +373,59 @@ static int gemm_plan_dma(const GP<bf16_t>& p, const GemmKnobs& k, int chains, Ge
     if (rc != 1) return rc;
     plan.n = 1;
     return gemm_glds_plan(p, k, chains, plan.l[0]);
+}
+
+// Two-output (C2) and two-operand (A2) launches: only the aligned register-staged 64x64 bf16 kernel implements them, so every
+// other shape or epilogue is an error here -- nothing falls through to a kernel that would ignore the second tensor.
+// A2 needs no kernel of its own: the last tap (offset 0, rows of A2 = launch rows, no in_len mask) is exactly the kernel's terminal
+// segment, the one that carries a rank extension U . Bl^T -- here with U = A2, R = K and Bl = that tap's K slice of W.  (A third
+// buffer descriptor selected per tap inside the loader cost 140 VGPRs and 992 bytes of scratch against 84 / 0.)
+template <typename T>
+static int gemm_plan_pair(const cvft_gemm_args* a, GP<T>& p, GemmPlan<T>& plan) {
+    if constexpr (sizeof(T) != 2) {
+        cvft_set_error("cvft_gemm: C2 / A2 launches are bf16 only");
+        return -1;
+    } else {
+        constexpr int VEC = 8;
+        const size_t lim = 0x7fff0000u;
+        const size_t bA = (size_t)(p.M / p.Tm) * p.Tin * p.lda * 2, bW = (size_t)p.N * p.ldw * 2;
+        const size_t bA2 = a->A2 ? (size_t)p.M * a->lda2 * 2 : 0;
+        // (xdrop_seed / the site fields mean nothing without xdrop_p / odrop_p and are not looked at)
+        const bool plain = !a->U && !a->La && !a->Bl && !a->Uout && !a->preact && !a->dact_src && a->act == 0 && a->xdrop_p <= 0.f &&
+                           a->odrop_p <= 0.f && !(p.C2 && a->A2) && !(p.C2 && a->residual);
+        const bool al = (p.K % VEC == 0) && (p.lda % VEC == 0) && (p.ldw % VEC == 0) && al16<T>(p.A) && al16<T>(p.W) &&
+                        (!a->A2 || ((a->lda2 % VEC == 0) && al16<T>(a->A2))) && bA < lim && bW < lim && bA2 < lim;
+        if (!plain || !al) {
+            cvft_set_error("cvft_gemm: a C2 / A2 launch takes 16-byte aligned bf16 operands, K %% 8 == 0, and no LoRA side path (U, La, Bl, Uout), activation, "
+                           "preact, dropout (nor a residual with C2, nor both at once)");
+            return -1;
+        }
+        p.R = 0; p.U = nullptr; p.Bl = nullptr; p.fuse = 0;
+        p.vecA = p.vecW = 1; p.vecU = p.vecB = 0;
+        p.bytesA = (unsigned)bA; p.bytesW = (unsigned)bW; p.bytesU = p.bytesB = 0;
+        if (p.C2) {
+            int ctr = -1;
+            for (int i = 0; i < p.ntaps; ++i) if (p.tap_off[i] == 0) ctr = i;
+            if (ctr < 0 || p.N1 <= 0 || p.N1 >= p.N || p.N1 % 64 != 0) {
+                cvft_set_error("cvft_gemm: C2 needs a tap with offset 0, 0 < N1 < N and N1 %% 64 == 0 (got N1 %d, N %d)", p.N1, p.N);
+                return -1;
+            }
+            p.ctr = ctr;
+            return gemm_plan_cfg<T, 64, 64, 2, 2, 4, true, false, 1>(p, plan);
+        }
+        if (p.ntaps < 2 || p.tap_off[p.ntaps - 1] != 0 || p.Tm != p.Tin || p.in_stride != 1) {
+            cvft_set_error("cvft_gemm: A2 is the operand of the LAST of ntaps >= 2 taps, offset 0, on stride-1 rows with Tm == Tin");
+            return -1;
+        }
+        const size_t skip = (size_t)(p.ntaps - 1) * p.K;         // elements in front of the last tap's slice in a row of W
+        p.ntaps -= 1;
+        p.U = (const T*)a->A2; p.ldu = a->lda2; p.R = p.K; p.bytesU = (unsigned)bA2;
+        p.Bl = p.W + skip; p.ldbl = p.ldw; p.bytesB = (unsigned)(bW - skip * 2);
+        p.vecU = p.vecB = 1;
+        const int rc = gemm_plan_cfg<T, 64, 64, 2, 2, 4, true>(p, plan);
+        snprintf(plan.l[0].label, sizeof(plan.l[0].label), "gemm_kernel<bf16,64,64,2,2>,two_in");
+        return rc;
+    }
 }
 
 // Fills GP from the (validated) arguments and chooses the launches.  Host arithmetic only: pointers are looked at for
@@ -384,6 +448,8 @@ static int gemm_plan(const cvft_gemm_args* a, const GemmKnobs& k, int chains, Ge
     p.xdrop_p = a->xdrop_p; p.xdrop_seed = (const long long*)a->xdrop_seed;
     for (int i = 0; i < 4; ++i) p.xdrop_sites[i] = a->xdrop_sites[i];
     p.odrop_p = a->odrop_p; p.odrop_site = a->odrop_site; p.row_off = 0;
+    p.C2 = (T*)a->C2; p.ldc2 = a->ldc2; p.bias2 = a->bias2; p.N1 = a->C2 ? a->N1 : a->N; p.ctr = 0;
+    if (p.C2 || a->A2) return gemm_plan_pair<T>(a, p, plan);
     if (p.odrop_p > 0.f) {
         if (!p.xdrop_seed || !cvft_drop_rate_ok(p.odrop_p) || p.N % 4 != 0 || p.ldc != p.N || !gemm_ident_out(p) || p.Tout != p.Tm) {
             cvft_set_error("cvft_gemm: output dropout needs a seed, 2^-16 <= p <= 1 - 2^-16, N %% 4 == 0, ldc == N and identity row geometry");
@@ -468,7 +534,9 @@ static int gemm_check_args(const cvft_gemm_args* a) {
     CVFT_CHECK_ARG(a->Tin > 0 && a->Tout > 0 && a->in_stride >= 1 && a->out_stride >= 1 && a->out_off >= 0,
                    "cvft_gemm: bad row geometry");
     CVFT_CHECK_ARG(a->A && a->W && a->C, "cvft_gemm: null operand");
-    CVFT_CHECK_ARG(a->lda >= a->K && a->ldw >= a->ntaps * a->K && a->ldc >= a->N, "cvft_gemm: bad leading dims");
+    CVFT_CHECK_ARG(a->lda >= a->K && a->ldw >= a->ntaps * a->K && a->ldc >= (a->C2 ? a->N1 : a->N), "cvft_gemm: bad leading dims");
+    CVFT_CHECK_ARG(!a->C2 || (a->N1 > 0 && a->N1 < a->N && a->ldc2 >= a->N - a->N1), "cvft_gemm: bad N1 / ldc2 of the second output");
+    CVFT_CHECK_ARG(!a->A2 || a->lda2 >= a->K, "cvft_gemm: bad lda2");
     if (a->La) {
         CVFT_CHECK_ARG(a->Bl && a->R > 0 && a->R <= 48 && a->ldla >= a->K && a->ldbl >= a->R, "cvft_gemm: fused LoRA needs 0 < R <= 48");
         CVFT_CHECK_ARG(a->ntaps == 1 && a->Tm == a->Tin && a->in_stride == 1 && a->tap_off[0] == 0 && a->out_stride == 1 &&

@@ -40,6 +40,8 @@ struct GP {
     float odrop_p; unsigned odrop_site;     // output dropout (cvft.h): C = residual + keep / (1 - p) * epi(.), seed = xdrop_seed; 0 = off
     int row_off;                  // rows in front of this launch's row 0 in the tensor the dropout masks index (a launch that computes a
                                   // row range of a larger product: gemm_p256_plan's row split); 0 otherwise
+    // two-output launch (cvft.h C2): column tiles at or beyond N1 run the centre tap `ctr` only and write C2 / bias2
+    T* C2; int ldc2; const float* bias2; int N1; int ctr;
 };
 
 // keep / (1 - p) factors of the output-dropout mask for the 4-element group holding flat output element `idx` (idx % 4 == 0)

@@ -218,6 +218,7 @@ __global__ void __launch_bounds__(512) gemm_fp8_kernel(GP<bf16_t> p, const unsig
 extern "C" int cvft_gemm_fp8(const cvft_gemm_args* a, const void* A8, int lda8, const float* a_scale, const void* W8, int ldw8,
                              const float* w_scale, void* stream) {
     CVFT_CHECK_ARG(a && A8 && W8 && a_scale && w_scale && a->C, "cvft_gemm_fp8: null operand");
+    CVFT_CHECK_ARG(!a->C2 && !a->A2, "cvft_gemm_fp8: no second output / second A operand");
     CVFT_CHECK_ARG(a->dtype == CVFT_BF16 && a->M > 0 && a->N > 0 && a->K > 0 && a->K % 128 == 0 && a->N % 4 == 0 && lda8 >= a->K &&
                    ldw8 >= a->K && lda8 % 16 == 0 && ldw8 % 16 == 0 && (((uintptr_t)A8 | (uintptr_t)W8) & 15) == 0 &&
                    ((uintptr_t)w_scale & 15) == 0,

@@ -410,7 +410,8 @@ __global__ void __launch_bounds__(256) gn_apply_fwd_kernel(int B, int T_, int C,
                                                             const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, const int* __restrict__ len,
                                                             const T* __restrict__ add, int apply_mish,
-                                                            T* __restrict__ y, const int* __restrict__ t_eff) {
+                                                            T* __restrict__ y, const int* __restrict__ t_eff,
+                                                            const T* __restrict__ res, int ldadd) {
     // one 16-byte chunk (VEC channels of one frame, all in one group since Cg % VEC == 0) per thread and step
     constexpr int VEC = VECP ? 16 / sizeof(T) : 1;
     const size_t total = (size_t)B * T_ * C / VEC;
@@ -424,13 +425,15 @@ __global__ void __launch_bounds__(256) gn_apply_fwd_kernel(int B, int T_, int C,
         const bool pad = t_eff && t >= *t_eff;                     // bucket padding: no such frame in the exact-shape batch
         const bool dead = (len && t >= len[b]) || pad;
         const size_t i = ch * VEC;
-        T xv[VEC], av[VEC], ov[VEC];
+        T xv[VEC], av[VEC], rv[VEC], ov[VEC];
         if (VECP) {
             *reinterpret_cast<uint4*>(xv) = *reinterpret_cast<const uint4*>(x + i);
-            if (add) *reinterpret_cast<uint4*>(av) = *reinterpret_cast<const uint4*>(add + (size_t)b * C + c0);
+            if (add) *reinterpret_cast<uint4*>(av) = *reinterpret_cast<const uint4*>(add + (size_t)b * ldadd + c0);
+            if (res) *reinterpret_cast<uint4*>(rv) = *reinterpret_cast<const uint4*>(res + i);
         } else {
             xv[0] = x[i];
-            if (add) av[0] = add[(size_t)b * C + c0];
+            if (add) av[0] = add[(size_t)b * ldadd + c0];
+            if (res) rv[0] = res[i];
         }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
@@ -439,6 +442,7 @@ __global__ void __launch_bounds__(256) gn_apply_fwd_kernel(int B, int T_, int C,
             float o = apply_mish ? act_apply(CVFT_ACT_MISH, z) : z;
             if (dead) o = 0.f;
             if (add && !pad) o += to_f32(av[k]);
+            if (res) o += to_f32(rv[k]);
             ov[k] = from_f32<T>(o);
         }
         if (VECP) *reinterpret_cast<uint4*>(y + i) = *reinterpret_cast<const uint4*>(ov);
@@ -565,12 +569,15 @@ constexpr int GN_NCH = 8;
 // MISH as a template flag and gamma / beta fetched per chunk BEFORE the element loop: with the run-time flag around them the
 // compiler kept one 4-byte load and one branch per element (128 / 368 scalar loads and 100-300 branches per thread in the
 // forward / backward kernels; a block is one of only B * G = 64 per launch, so its own instruction stream is the launch time).
-template <typename T, bool MISH, int NCH>
+// RES: a residual stream res [B*T][C] joins after Mish and the mask, on every frame (bucket padding included: the caller's res
+// carries what those frames must hold) -- one more 16-byte read per chunk, the fp32 sum is rounded once.
+template <typename T, bool MISH, int NCH, bool RES = false>
 __global__ void __launch_bounds__(512) gn_fused_fwd_kernel(int T_, int C, int G, const T* __restrict__ x,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             float eps, const int* __restrict__ len, const T* __restrict__ add,
                                                             T* __restrict__ y, float* __restrict__ mean,
-                                                            float* __restrict__ rstd, const int* __restrict__ t_eff) {
+                                                            float* __restrict__ rstd, const int* __restrict__ t_eff,
+                                                            const T* __restrict__ res, int ldadd) {
     constexpr int VEC = 16 / sizeof(T);
     __shared__ float sm[16];
     const int b = blockIdx.x / G, g = blockIdx.x % G;
@@ -626,7 +633,9 @@ __global__ void __launch_bounds__(512) gn_fused_fwd_kernel(int T_, int C, int G,
         const bool dead = t >= lb || pad;
         const T* ve = reinterpret_cast<const T*>(&xr[k]);
         T av[VEC], ov[VEC];
-        *reinterpret_cast<uint4*>(av) = add ? *reinterpret_cast<const uint4*>(add + (size_t)b * C + c0) : make_uint4(0, 0, 0, 0);
+        *reinterpret_cast<uint4*>(av) = add ? *reinterpret_cast<const uint4*>(add + (size_t)b * ldadd + c0) : make_uint4(0, 0, 0, 0);
+        T rv[VEC];
+        if (RES) *reinterpret_cast<uint4*>(rv) = *reinterpret_cast<const uint4*>(res + off + (size_t)t * C + cc);
         if (!same_c) {
 #pragma unroll
             for (int q = 0; q < VEC; ++q) { gm[q] = gamma[c0 + q]; bt[q] = beta[c0 + q]; }
@@ -637,6 +646,7 @@ __global__ void __launch_bounds__(512) gn_fused_fwd_kernel(int T_, int C, int G,
             float o = MISH ? act_apply(CVFT_ACT_MISH, z) : z;
             o = dead ? 0.f : o;
             o += pad ? 0.f : to_f32(av[q]);
+            if (RES) o += to_f32(rv[q]);
             ov[q] = from_f32<T>(o);
         }
         *reinterpret_cast<uint4*>(y + off + (size_t)t * C + cc) = *reinterpret_cast<const uint4*>(ov);
@@ -736,9 +746,9 @@ static inline unsigned ew_grid(size_t total) {
     return (unsigned)(g > 4096 ? 4096 : (g == 0 ? 1 : g));
 }
 
-extern "C" int cvft_groupnorm_mish_fwd(int dtype, int B, int T, int C, int G, const void* x, const float* gamma,
-                                       const float* beta, float eps, const int32_t* len, const void* add,
-                                       int apply_mish, void* y, float* mean, float* rstd, const int32_t* t_eff, void* stream) {
+static int gn_fwd(int dtype, int B, int T, int C, int G, const void* x, const float* gamma,
+                  const float* beta, float eps, const int32_t* len, const void* add, int ldadd,
+                  int apply_mish, const void* res, void* y, float* mean, float* rstd, const int32_t* t_eff, void* stream) {
     CVFT_CHECK_ARG(dtype == CVFT_F32 || dtype == CVFT_BF16, "cvft_groupnorm_mish_fwd: bad dtype");
     CVFT_CHECK_ARG(B > 0 && T > 0 && C > 0 && G > 0 && C % G == 0, "cvft_groupnorm_mish_fwd: bad dims B%d T%d C%d G%d", B, T, C, G);
     CVFT_CHECK_ARG(x && gamma && beta && y && mean && rstd, "cvft_groupnorm_mish_fwd: null operand");
@@ -746,16 +756,19 @@ extern "C" int cvft_groupnorm_mish_fwd(int dtype, int B, int T, int C, int G, co
     size_t total = (size_t)B * T * C;
     const int vec = dtype == CVFT_F32 ? 4 : 8;
     const bool vp = ((C / G) % vec == 0) && (C % vec == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-    const bool vpa = vp && ((reinterpret_cast<uintptr_t>(y) & 15) == 0) && (!add || ((reinterpret_cast<uintptr_t>(add) & 15) == 0));
+    CVFT_CHECK_ARG(!add || ldadd >= C, "cvft_groupnorm_mish_fwd: bad ldadd %d", ldadd);
+    const bool vpa = vp && ((reinterpret_cast<uintptr_t>(y) & 15) == 0) && (!res || ((reinterpret_cast<uintptr_t>(res) & 15) == 0)) &&
+                     (!add || (((reinterpret_cast<uintptr_t>(add) & 15) == 0) && ldadd % vec == 0));
     if (gn_fused_ok(T, C / G, vec, vpa)) {
         // chunks per thread the kernel is unrolled for: 4 cover the estimator's slabs (500 frames x 4 chunks) with half the registers
         const bool half = (long)T * (C / G / vec) <= 512L * (GN_NCH / 2);
-#define GN_FF(TT, MI) do { if (half) hipLaunchKernelGGL((gn_fused_fwd_kernel<TT, MI, GN_NCH / 2>), dim3(B * G), dim3(512), 0, st, T, C, G, (const TT*)x, gamma, beta, eps, \
-                                         len, (const TT*)add, (TT*)y, mean, rstd, t_eff);                                                   \
-                           else hipLaunchKernelGGL((gn_fused_fwd_kernel<TT, MI, GN_NCH>), dim3(B * G), dim3(512), 0, st, T, C, G, (const TT*)x, gamma, beta, eps, \
-                                         len, (const TT*)add, (TT*)y, mean, rstd, t_eff); } while (0)
+#define GN_FK(TT, MI, NC, RS) hipLaunchKernelGGL((gn_fused_fwd_kernel<TT, MI, NC, RS>), dim3(B * G), dim3(512), 0, st, T, C, G, (const TT*)x, gamma, beta, eps, \
+                                                len, (const TT*)add, (TT*)y, mean, rstd, t_eff, (const TT*)res, ldadd)
+#define GN_FF(TT, MI) do { if (half) { if (res) GN_FK(TT, MI, GN_NCH / 2, true); else GN_FK(TT, MI, GN_NCH / 2, false); }     \
+                           else { if (res) GN_FK(TT, MI, GN_NCH, true); else GN_FK(TT, MI, GN_NCH, false); } } while (0)
         if (dtype == CVFT_F32) { if (apply_mish) GN_FF(float, true); else GN_FF(float, false); }
         else { if (apply_mish) GN_FF(bf16_t, true); else GN_FF(bf16_t, false); }
+#undef GN_FK
 #undef GN_FF
         CVFT_LAUNCH_CHECK("cvft_groupnorm_mish_fwd");
         return 0;
@@ -764,19 +777,32 @@ extern "C" int cvft_groupnorm_mish_fwd(int dtype, int B, int T, int C, int G, co
         if (vp) hipLaunchKernelGGL((gn_stats_kernel<float, true>), dim3(B * G), dim3(512), 0, st, T, C, G, (const float*)x, eps, mean, rstd, t_eff);
         else hipLaunchKernelGGL((gn_stats_kernel<float, false>), dim3(B * G), dim3(512), 0, st, T, C, G, (const float*)x, eps, mean, rstd, t_eff);
         if (vpa) hipLaunchKernelGGL((gn_apply_fwd_kernel<float, true>), dim3(ew_grid(total / vec)), dim3(256), 0, st, B, T, C, G,
-                                    (const float*)x, gamma, beta, mean, rstd, len, (const float*)add, apply_mish, (float*)y, t_eff);
+                                    (const float*)x, gamma, beta, mean, rstd, len, (const float*)add, apply_mish, (float*)y, t_eff, (const float*)res, ldadd);
         else hipLaunchKernelGGL((gn_apply_fwd_kernel<float, false>), dim3(ew_grid(total)), dim3(256), 0, st, B, T, C, G,
-                                (const float*)x, gamma, beta, mean, rstd, len, (const float*)add, apply_mish, (float*)y, t_eff);
+                                (const float*)x, gamma, beta, mean, rstd, len, (const float*)add, apply_mish, (float*)y, t_eff, (const float*)res, ldadd);
     } else {
         if (vp) hipLaunchKernelGGL((gn_stats_kernel<bf16_t, true>), dim3(B * G), dim3(512), 0, st, T, C, G, (const bf16_t*)x, eps, mean, rstd, t_eff);
         else hipLaunchKernelGGL((gn_stats_kernel<bf16_t, false>), dim3(B * G), dim3(512), 0, st, T, C, G, (const bf16_t*)x, eps, mean, rstd, t_eff);
         if (vpa) hipLaunchKernelGGL((gn_apply_fwd_kernel<bf16_t, true>), dim3(ew_grid(total / vec)), dim3(256), 0, st, B, T, C, G,
-                                    (const bf16_t*)x, gamma, beta, mean, rstd, len, (const bf16_t*)add, apply_mish, (bf16_t*)y, t_eff);
+                                    (const bf16_t*)x, gamma, beta, mean, rstd, len, (const bf16_t*)add, apply_mish, (bf16_t*)y, t_eff, (const bf16_t*)res, ldadd);
         else hipLaunchKernelGGL((gn_apply_fwd_kernel<bf16_t, false>), dim3(ew_grid(total)), dim3(256), 0, st, B, T, C, G,
-                                (const bf16_t*)x, gamma, beta, mean, rstd, len, (const bf16_t*)add, apply_mish, (bf16_t*)y, t_eff);
+                                (const bf16_t*)x, gamma, beta, mean, rstd, len, (const bf16_t*)add, apply_mish, (bf16_t*)y, t_eff, (const bf16_t*)res, ldadd);
     }
     CVFT_LAUNCH_CHECK("cvft_groupnorm_mish_fwd");
     return 0;
+}
+
+extern "C" int cvft_groupnorm_mish_fwd(int dtype, int B, int T, int C, int G, const void* x, const float* gamma,
+                                       const float* beta, float eps, const int32_t* len, const void* add,
+                                       int apply_mish, void* y, float* mean, float* rstd, const int32_t* t_eff, void* stream) {
+    return gn_fwd(dtype, B, T, C, G, x, gamma, beta, eps, len, add, C, apply_mish, nullptr, y, mean, rstd, t_eff, stream);
+}
+
+extern "C" int cvft_groupnorm_mish_res_fwd(int dtype, int B, int T, int C, int G, const void* x, const float* gamma,
+                                           const float* beta, float eps, const int32_t* len, const void* add, int ldadd,
+                                           int apply_mish, const void* res, void* y, float* mean, float* rstd,
+                                           const int32_t* t_eff, void* stream) {
+    return gn_fwd(dtype, B, T, C, G, x, gamma, beta, eps, len, add, ldadd, apply_mish, res, y, mean, rstd, t_eff, stream);
 }
 
 extern "C" int cvft_groupnorm_mish_bwd(int dtype, int B, int T, int C, int G, const void* x, const float* gamma,

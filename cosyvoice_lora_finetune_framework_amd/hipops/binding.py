@@ -104,6 +104,8 @@ class GemmArgs(C.Structure):
         ("La", C.c_void_p), ("ldla", C.c_int), ("lora_scale", C.c_float), ("Uout", C.c_void_p),
         ("xdrop_p", C.c_float), ("xdrop_seed", C.c_void_p), ("xdrop_sites", C.c_uint * 4),
         ("odrop_p", C.c_float), ("odrop_site", C.c_uint),
+        ("C2", C.c_void_p), ("ldc2", C.c_int), ("bias2", C.c_void_p), ("N1", C.c_int),
+        ("A2", C.c_void_p), ("lda2", C.c_int),
     ]
 
 
@@ -149,6 +151,7 @@ SIGNATURES = {
     "cvft_layernorm_bwd_mask": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, C.c_uint, _p, _p],
     "cvft_layernorm_bwd_mask_side": [_i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, C.c_uint, _p, _p, _i, _f, _p, _p],
     "cvft_groupnorm_mish_fwd": [_i, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p, _i, _p, _p, _p, _p, _p],
+    "cvft_groupnorm_mish_res_fwd": [_i, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p],
     "cvft_groupnorm_mish_bwd": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p],
     "cvft_attn_bias_fwd": [_i, _i, _i, _i, _p, _p, _p, _i, _p, _f, _i, _p, _i, _p, _p, _p],
     "cvft_attn_bias_bwd": [_i, _i, _i, _i, _p, _p, _p, _i, _p, _f, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p],

@@ -78,8 +78,12 @@ def gemm(x: torch.Tensor, W: torch.Tensor, *, N: Optional[int] = None, K: Option
          geo: Optional[Geo] = None, nb: int = 1, in_len: Optional[torch.Tensor] = None,
          out_len: Optional[torch.Tensor] = None, out_rows: Optional[int] = None,
          La: Optional[torch.Tensor] = None, lora_scale: float = 1.0, Uout: Optional[torch.Tensor] = None,
-         xdrop=None, odrop=None) -> torch.Tensor:
+         xdrop=None, odrop=None, out2: Optional[torch.Tensor] = None, bias2: Optional[torch.Tensor] = None,
+         x2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C = epi(alpha * (taps(x) @ W^T + U @ Bl^T) + bias); W is [N][ntaps*K] (k contiguous).
+    out2 (+ bias2): second output of a two-output launch -- the last out2.shape[1] rows of W use the offset-0 tap only and are
+    written there (cvft.h C2); `out` is then required and holds the first N - out2.shape[1] columns.
+    x2: the last tap reads x2 instead of x, free of in_len (cvft.h A2).
     odrop = (p, site): output dropout in the epilogue, C = residual + keep(site) / (1 - p) * epi(.) (cvft.h).
     xdrop = (p, sites): the U Bl^T term enters per 16-wide rank tile t as mask_t / (1 - p) * (U_t Bl_t^T), masks over the
     output elements (the lora_dropout dgrad; include/cvft.h)."""
@@ -114,12 +118,13 @@ def gemm(x: torch.Tensor, W: torch.Tensor, *, N: Optional[int] = None, K: Option
             assert Uout.shape[0] == a.M and Uout.shape[1] >= a.R
             a.Uout, a.ldu = ptr(Uout), Uout.stride(0)
     if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() >= N
+        assert bias.dtype == torch.float32 and bias.numel() >= (N if out2 is None else N - out2.shape[1])
     a.bias, a.alpha, a.act = ptr(bias), float(alpha), ACT[act]
     if out is None:
+        assert out2 is None
         rows = nb * geo.Tout if out_rows is None else out_rows
         out = torch.empty((rows, N), dtype=x.dtype, device=x.device)
-    assert out.shape[0] == nb * geo.Tout and out.shape[1] >= N
+    assert out.shape[0] == nb * geo.Tout and out.shape[1] >= (N if out2 is None else N - out2.shape[1])
     if preact is not None:
         a.preact, a.ldp = ptr(preact), preact.stride(0)
     if dact_src is not None:
@@ -128,6 +133,13 @@ def gemm(x: torch.Tensor, W: torch.Tensor, *, N: Optional[int] = None, K: Option
         assert residual.shape[0] == out.shape[0]
         a.residual, a.ldr = ptr(residual), residual.stride(0)
     a.C, a.ldc = ptr(out), out.stride(0)
+    if out2 is not None:
+        assert out2.shape[0] == out.shape[0] and out2.dtype == x.dtype and 0 < out2.shape[1] < N
+        assert bias2 is None or (bias2.dtype == torch.float32 and bias2.numel() >= out2.shape[1])
+        a.C2, a.ldc2, a.bias2, a.N1 = ptr(out2), out2.stride(0), ptr(bias2), N - out2.shape[1]
+    if x2 is not None:
+        assert x2.shape[0] == x.shape[0] and x2.shape[1] >= K and x2.dtype == x.dtype
+        a.A2, a.lda2 = ptr(x2), x2.stride(0)
     if xdrop is not None:
         assert U is not None and U.shape[1] % 16 == 0 and len(xdrop[1]) == U.shape[1] // 16
         a.xdrop_p, a.xdrop_seed = float(xdrop[0]), ptr(_DROPOUT["seed"])
@@ -1965,6 +1977,71 @@ class ConvFn(torch.autograd.Function):
         return dx, dres, None, None, None, None, None, None, None
 
 
+# The same pair as ONE launch each way (ResnetBlock1D, CVFT_RESNET_FOLD): forward, the k = 3 convolution and the 1x1 shortcut read
+# the same masked x -- the shortcut's output columns ride as extra column tiles that walk the centre tap only; backward, the
+# shortcut's input gradient is a fourth tap of the k = 3 dgrad reading the block-output gradient.  No parked tensor, no token.
+RESNET_FOLD = _os.environ.get("CVFT_RESNET_FOLD", "1")         # 0 separate launches, 1 folded; "conv" / "temb": one part only (A/B)
+RESNET_FOLD_CONV = RESNET_FOLD in ("1", "conv")
+RESNET_FOLD_TEMB = RESNET_FOLD in ("1", "temb")
+
+
+def conv_pair_weights(w3: torch.Tensor, w1: torch.Tensor, dtype: torch.dtype):
+    """w3 [Cout][Cin][3] (pad 1), w1 [Cout2][Cin][1] -> (Wf [Cout + Cout2][3*Cin], Wb [Cin][3*Cout + Cout2]).
+    Wf: tap-major rows of the k = 3 conv, then the shortcut's rows with their weights in the centre-tap slice (the other two
+    slices are never read by the launch; zeros).  Wb: the k = 3 dgrad's three flipped slices, then the shortcut's transpose as
+    the fourth (offset-0) tap.  Needs Cout2's dgrad K == Cout's: the two gradients have the same width."""
+    w3, w1 = w3.detach().to(torch.float64), w1.detach().to(torch.float64)
+    N1, Cin, k = w3.shape
+    N2 = w1.shape[0]
+    assert k == 3 and w1.shape[1] == Cin and w1.shape[2] == 1 and N1 == N2
+    Wf = w3.new_zeros((N1 + N2, 3 * Cin))
+    Wf[:N1] = w3.permute(0, 2, 1).reshape(N1, 3 * Cin)
+    Wf[N1:, Cin:2 * Cin] = w1[:, :, 0]
+    Wb = torch.cat([w3.flip(2).permute(1, 2, 0).reshape(Cin, 3 * N1), w1[:, :, 0].t()], dim=1)
+    return Wf.to(dtype).contiguous(), Wb.to(dtype).contiguous()
+
+
+class ConvPairPack:
+    def __init__(self, conv3, conv1, dtype: torch.dtype):
+        self.N1, self.Cin, self.N2 = conv3.weight.shape[0], conv3.weight.shape[1], conv1.weight.shape[0]
+        self.Wf, self.Wb = conv_pair_weights(conv3.weight, conv1.weight, dtype)
+        self.bias = None if conv3.bias is None else conv3.bias.detach().float().contiguous()
+        self.bias2 = None if conv1.bias is None else conv1.bias.detach().float().contiguous()
+
+
+def can_conv_pair(x: torch.Tensor, Cin: int, N1: int, N2: int) -> bool:
+    """The shapes the two-output / two-operand launches take (gemm_plan_pair in csrc/gemm.hip): anything else is an error there."""
+    return (x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == Cin and x.is_contiguous() and x.data_ptr() % 16 == 0
+            and Cin % 8 == 0 and N1 % 64 == 0 and N1 == N2)
+
+
+class ConvPairFn(torch.autograd.Function):
+    """(conv3(x * mask), conv1(x * mask)) -> ([B*T, N1], [B*T, N2]); frozen weights."""
+
+    @staticmethod
+    def forward(ctx, x, pack: ConvPairPack, B: int, T: int, in_len):
+        h = torch.empty((B * T, pack.N1), dtype=x.dtype, device=x.device)
+        r = torch.empty((B * T, pack.N2), dtype=x.dtype, device=x.device)
+        gemm(x, pack.Wf, K=pack.Cin, bias=pack.bias, geo=Geo(Tm=T, Tin=T, Tout=T, taps=(-1, 0, 1)), nb=B, in_len=in_len,
+             out=h, out2=r, bias2=pack.bias2)
+        ctx.pack, ctx.B, ctx.T, ctx.in_len = pack, B, T, in_len
+        return h, r
+
+    @staticmethod
+    def backward(ctx, dh, dr):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        pack, B, T = ctx.pack, ctx.B, ctx.T
+        # dx[t] = sum_j dh[t + j - 1] . w3[:, :, 2 - j] + dr[t] . w1;  forward's input mask zeroes dx rows >= in_len
+        dx = gemm(_c(dh), pack.Wb, N=pack.Cin, K=pack.N1, geo=Geo(Tm=T, Tin=T, Tout=T, taps=(-1, 0, 1, 0)), nb=B,
+                  out_len=ctx.in_len, x2=_c(dr))
+        return dx, None, None, None, None
+
+
+def conv_pair(x, pack: ConvPairPack, B: int, T: int, in_len=None):
+    return ConvPairFn.apply(x, pack, B, T, in_len)
+
+
 def conv1d(x, pack: ConvPack, B: int, Tin: int, Tout: Optional[int] = None, in_len=None, out_len=None, residual=None, fork=None):
     """x [B*Tin, Cin] -> [B*Tout, Cout]; in_len masks input frames (x*mask), out_len zeroes output frames;
     `residual` [B*Tout, Cout] is added in the GEMM epilogue (stride-1 convs, no out_len).
@@ -2069,16 +2146,28 @@ def layernorm_fork(x, gamma, beta, eps: float = 1e-5, side=None):
 
 class GroupNormMishFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, B: int, T: int, G: int, eps: float, length, add, mish: bool, t_eff=None):
+    def forward(ctx, x, gamma, beta, B: int, T: int, G: int, eps: float, length, add, mish: bool, t_eff=None, res=None):
         x = _c(x)
         Cn = x.shape[1]
         assert x.shape[0] == B * T
         y = torch.empty_like(x)
         mean = torch.empty(B * G, dtype=torch.float32, device=x.device)
         rstd = torch.empty(B * G, dtype=torch.float32, device=x.device)
-        check(lib().cvft_groupnorm_mish_fwd(dt(x), B, T, Cn, G, ptr(x), ptr(gamma), ptr(beta), eps, ptr(length),
-                                            ptr(None if add is None else _c(add)), int(mish), ptr(y), ptr(mean),
-                                            ptr(rstd), ptr(t_eff), stream()), "cvft_groupnorm_mish_fwd")
+        if add is not None and add.dim() == 2 and add.stride(1) == 1 and add.stride(0) >= Cn:
+            ldadd = add.stride(0)                  # a column slice of a wider [B, .] tensor is read in place
+        else:
+            add, ldadd = (None if add is None else _c(add)), Cn
+        if res is None and ldadd == Cn:
+            check(lib().cvft_groupnorm_mish_fwd(dt(x), B, T, Cn, G, ptr(x), ptr(gamma), ptr(beta), eps, ptr(length),
+                                                ptr(add), int(mish), ptr(y), ptr(mean),
+                                                ptr(rstd), ptr(t_eff), stream()), "cvft_groupnorm_mish_fwd")
+        else:
+            if res is not None:
+                res = _c(res)
+                assert res.shape == x.shape and res.dtype == x.dtype
+            check(lib().cvft_groupnorm_mish_res_fwd(dt(x), B, T, Cn, G, ptr(x), ptr(gamma), ptr(beta), eps, ptr(length),
+                                                    ptr(add), ldadd, int(mish), ptr(res), ptr(y), ptr(mean),
+                                                    ptr(rstd), ptr(t_eff), stream()), "cvft_groupnorm_mish_res_fwd")
         ctx.save_for_backward(x, gamma, beta, mean, rstd)
         ctx.dims, ctx.length, ctx.mish, ctx.t_eff = (B, T, Cn, G), length, mish, t_eff
         return y
@@ -2093,14 +2182,16 @@ class GroupNormMishFn(torch.autograd.Function):
         check(lib().cvft_groupnorm_mish_bwd(dt(x), B, T, Cn, G, ptr(x), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
                                             ptr(ctx.length), int(ctx.mish), ptr(dy), ptr(dx), ptr(ws), ptr(ctx.t_eff), stream()),
               "cvft_groupnorm_mish_bwd")
-        return dx, None, None, None, None, None, None, None, None, None, None
+        # (the residual joins after Mish and the mask: its gradient is dy itself)
+        return dx, None, None, None, None, None, None, None, None, None, None, (dy if ctx.needs_input_grad[11] else None)
 
 
 def groupnorm_mish(x, gamma, beta, B: int, T: int, G: int, eps: float = 1e-5, length=None, add=None, mish: bool = True,
-                   t_eff=None):
-    """x [B*T, C] channel-last; y = mish(GN(x)) * (t < length[b]) + add[b]  (add carries no gradient).
+                   t_eff=None, res=None):
+    """x [B*T, C] channel-last; y = mish(GN(x)) * (t < length[b]) + add[b] + res  (add carries no gradient; it may be a column
+    slice of a wider [B, .] tensor).  res [B*T, C] (optional) joins on every frame and receives dy as its gradient.
     t_eff (device int32[1], optional): the exact batch's frame count when T is padded to a shape bucket (cvft.h)."""
-    return GroupNormMishFn.apply(x, gamma, beta, B, T, G, eps, length, add, mish, t_eff)
+    return GroupNormMishFn.apply(x, gamma, beta, B, T, G, eps, length, add, mish, t_eff, res)
 
 
 # ---------------------------------------------------------------------------------

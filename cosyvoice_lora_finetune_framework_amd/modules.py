@@ -247,10 +247,14 @@ class Block1D(nn.Module):
         super().__init__()
         self.block = nn.Sequential(nn.Conv1d(dim, dim_out, 3, padding=1), nn.GroupNorm(groups, dim_out), nn.Mish())
 
-    def forward(self, x, B, T, length, add=None, t_eff=None, fork=None):
+    def forward(self, x, B, T, length, add=None, t_eff=None, fork=None, res=None):
         conv, gn = self.block[0], self.block[1]
         h = HF.conv1d(x, conv_pack(conv, x.dtype), B, T, in_len=length, fork=fork)
-        return HF.groupnorm_mish(h, _f32(gn.weight), _f32(gn.bias), B, T, gn.num_groups, gn.eps, length, add, True, t_eff)
+        return self.norm_act(h, B, T, length, add, t_eff, res)
+
+    def norm_act(self, h, B, T, length, add=None, t_eff=None, res=None):
+        gn = self.block[1]
+        return HF.groupnorm_mish(h, _f32(gn.weight), _f32(gn.bias), B, T, gn.num_groups, gn.eps, length, add, True, t_eff, res)
 
 
 class ResnetBlock1D(nn.Module):
@@ -263,9 +267,44 @@ class ResnetBlock1D(nn.Module):
         self.block2 = Block1D(dim_out, dim_out, groups=groups)
         self.res_conv = nn.Conv1d(dim, dim_out, 1)
 
-    def forward(self, x, B, T, length, temb_mish, t_eff=None):
-        with torch.no_grad():
-            add = hip_linear(self.mlp[1], temb_mish)                       # [B, dim_out]; depends on t only
+    def time_proj_stackable(self) -> bool:
+        """mlp[1] is a plain frozen nn.Linear: its projection may be computed together with the other blocks' (stacked_time_proj)."""
+        lin = self.mlp[1]
+        return type(lin) is nn.Linear and lin.bias is not None and not lin.weight.requires_grad and not lin.bias.requires_grad
+
+    def _pair_pack(self, x):
+        """ConvPairPack of (block1's conv, res_conv) when the two run as one launch each way (HF.conv_pair), else None: plain
+        stride-1 convolutions without adapters, bf16, shapes the pair launches take."""
+        c3, c2, c1 = self.block1.block[0], self.block2.block[0], self.res_conv
+
+        def plain(c, k):
+            return (type(c) is nn.Conv1d and c.kernel_size == (k,) and c.stride == (1,) and c.padding == ((k - 1) // 2,)
+                    and c.dilation == (1,) and c.groups == 1 and c.padding_mode == "zeros")
+        if not (plain(c3, 3) and plain(c2, 3) and plain(c1, 1)
+                and HF.can_conv_pair(x, c3.in_channels, c3.out_channels, c1.out_channels)):
+            return None
+        tag = (x.dtype, c3.weight._version, c3.weight.data_ptr(), c1.weight._version, c1.weight.data_ptr(),
+               None if c3.bias is None else (c3.bias._version, c3.bias.data_ptr()),
+               None if c1.bias is None else (c1.bias._version, c1.bias.data_ptr()))
+        hit = self.__dict__.get("_cvft_pair")
+        if hit is None or hit[0] != tag:
+            hit = (tag, HF.ConvPairPack(c3, c1, x.dtype))
+            self.__dict__["_cvft_pair"] = hit
+        return hit[1]
+
+    def forward(self, x, B, T, length, temb_mish, t_eff=None, add=None, fold=False):
+        """add: this block's time projection when the decoder computed all of them in one launch (_stacked_time_proj).
+        fold: the caller asks for the pair launches (the decoder does, under CVFT_RESNET_FOLD); a block that cannot take them
+        (_pair_pack) and a block called without it run the separate launches with the `fork` hand-over, bit for bit as before."""
+        if add is None:
+            with torch.no_grad():
+                add = hip_linear(self.mlp[1], temb_mish)                   # [B, dim_out]; depends on t only
+        pair = self._pair_pack(x) if fold else None
+        if pair is not None:
+            # one launch for block1's conv and res_conv(x * mask); the sum h + shortcut forms in block2's GroupNorm + Mish launch
+            h, r = HF.conv_pair(x, pair, B, T, length)
+            h = self.block1.norm_act(h, B, T, length, add=add, t_eff=t_eff)
+            return self.block2(h, B, T, length, t_eff=t_eff, res=r)
         # x feeds block1's conv and res_conv: the two input gradients meet inside block1's dgrad launch (HF.conv1d `fork`)
         h = self.block1(x, B, T, length, add=add, t_eff=t_eff, fork="take")
         h = self.block2(h, B, T, length, t_eff=t_eff)
@@ -465,6 +504,33 @@ class ConditionalDecoder(nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
+    def _resnets(self):
+        return [b[0] for b in self.down_blocks] + [b[0] for b in self.mid_blocks] + [b[0] for b in self.up_blocks]
+
+    def _stacked_time_proj(self, temb_mish):
+        """Per resnet (forward order) its time projection mlp[1](temb_mish) [B, dim_out], or None where the block computes its
+        own.  The projections of all blocks whose mlp[1] is a plain frozen Linear share their input: ONE GEMM against the
+        stacked weights, each block reading its column slice in place (HF.groupnorm_mish takes the pitch).  Call under no_grad."""
+        resnets = self._resnets()
+        idx = [i for i, r in enumerate(resnets) if r.time_proj_stackable() and r.mlp[1].out_features % 8 == 0
+               and r.mlp[1].in_features == temb_mish.shape[1]] if (HF.RESNET_FOLD_TEMB and temb_mish.dtype == torch.bfloat16) else []
+        out = [None] * len(resnets)
+        if len(idx) < 2:
+            return out
+        lins = [resnets[i].mlp[1] for i in idx]
+        tag = (temb_mish.dtype,) + tuple((l.weight._version, l.weight.data_ptr(), l.bias._version, l.bias.data_ptr()) for l in lins)
+        hit = self.__dict__.get("_cvft_temb_stack")
+        if hit is None or hit[0] != tag:
+            hit = (tag, HF.LinearPack(torch.cat([l.weight.detach() for l in lins], dim=0),
+                                      torch.cat([l.bias.detach() for l in lins], dim=0), temb_mish.dtype))
+            self.__dict__["_cvft_temb_stack"] = hit
+        y = HF.lora_linear(temb_mish, hit[1])
+        o = 0
+        for i, l in zip(idx, lins):
+            out[i] = y[:, o:o + l.out_features]
+            o += l.out_features
+        return out
+
     def forward_cl(self, xin, t, B: int, T: int, length, gelu: str = "gelu_erf", t_true=None):
         """xin [B*T, in_channels] (already [y|mu|spk|cond] packed), t [B] fp32, length int32 [B]
         -> [B*T, out_channels] (masked).
@@ -483,12 +549,13 @@ class ConditionalDecoder(nn.Module):
         with torch.no_grad():
             temb = self.time_mlp(self.time_embeddings(t, dtype=dtype))
             temb_mish = HF.act_fwd(temb, "mish")
+            adds = iter(self._stacked_time_proj(temb_mish))
         x = xin
         hiddens: List[Tuple[torch.Tensor, int, torch.Tensor, int]] = []
         Tc, lc, lv = T, length, 0
         te = (lambda l: None) if t_true is None else (lambda l: t_true[l:l + 1])
         for resnet, tblocks, down in self.down_blocks:
-            x = resnet(x, B, Tc, lc, temb_mish, te(lv))
+            x = resnet(x, B, Tc, lc, temb_mish, te(lv), next(adds), HF.RESNET_FOLD_CONV)
             for i, tb in enumerate(tblocks):
                 x = tb(x, B, Tc, lc, gelu, iso(Tc), tblocks[i + 1] if i + 1 < len(tblocks) else None)
             hiddens.append((x, Tc, lc, lv))
@@ -501,14 +568,14 @@ class ConditionalDecoder(nn.Module):
                 x = HF.conv1d(x, conv_pack(down, dtype), B, Tc, in_len=lc)
                 # reference appends mask_down[:, :, ::2] then drops it (masks = masks[:-1])
         for resnet, tblocks in self.mid_blocks:
-            x = resnet(x, B, Tc, lc, temb_mish, te(lv))
+            x = resnet(x, B, Tc, lc, temb_mish, te(lv), next(adds), HF.RESNET_FOLD_CONV)
             for i, tb in enumerate(tblocks):
                 x = tb(x, B, Tc, lc, gelu, iso(Tc), tblocks[i + 1] if i + 1 < len(tblocks) else None)
         for resnet, tblocks, up in self.up_blocks:
             skip, Ts, ls, lvs = hiddens.pop()
             assert Ts == Tc, (Ts, Tc)
             x = torch.cat([x, skip], dim=1)
-            x = resnet(x, B, Ts, ls, temb_mish, te(lvs))
+            x = resnet(x, B, Ts, ls, temb_mish, te(lvs), next(adds), HF.RESNET_FOLD_CONV)
             for i, tb in enumerate(tblocks):
                 x = tb(x, B, Ts, ls, gelu, iso(Ts), tblocks[i + 1] if i + 1 < len(tblocks) else None)
             if isinstance(up, Upsample1D):

@@ -96,6 +96,18 @@ typedef struct {
      * the one cvft_dropout_add(site) applies to a contiguous [M, N] tensor (its backward).  Needs N % 4 == 0, ldc == N,
      * identity row geometry and a seed; every GEMM kernel honours it. */
     float odrop_p; unsigned odrop_site;
+    /* second output (version >= 103; a k-tap convolution and the 1x1 convolution of the same masked input in one launch): when
+     * C2 != NULL the launch covers N = N1 + N2 columns and W is [N][ntaps*K].  Columns n < N1 are the product above, written to
+     * C with bias[n].  Columns n >= N1 use ONLY the tap whose offset is 0 (rows N1.. of W hold their weights in that tap's K
+     * slice; the other slices are never read) and go to C2[orow, n - N1] with bias2[n - N1].  Both outputs share the row
+     * geometry and the masks.  bf16, N1 % 64 == 0, 16-byte aligned operands, no side path / activation / preact / dropout /
+     * residual; any other request is an error. */
+    void* C2; int ldc2; const float* bias2; int N1;
+    /* second A operand (version >= 103; the two input gradients of that pair in one launch): when A2 != NULL the LAST tap reads
+     * row m of A2 [M][lda2] instead of A, and in_len does not mask it.  That tap's offset is 0 and the rows are stride-1 with
+     * Tm == Tin, so launch row m IS the row the tap reads.  Same restrictions as C2 except that a residual is allowed; C2 and
+     * A2 exclude each other. */
+    const void* A2; int lda2;
 } cvft_gemm_args;
 
 int cvft_gemm(const cvft_gemm_args* a, void* stream);
@@ -226,6 +238,16 @@ int cvft_groupnorm_mish_fwd(int dtype, int B, int T, int C, int G, const void* x
                             const float* beta, float eps, const int32_t* len, const void* add /*[B][C] dtype or NULL*/,
                             int apply_mish, void* y, float* mean /*[B*G]*/, float* rstd /*[B*G]*/,
                             const int32_t* t_eff /*device int or NULL*/, void* stream);
+/* (version >= 103) the same launch with a row pitch for add (rows b of a wider [B][ldadd] tensor: column slices are consumed in
+ * place) and an optional residual stream res [B][T][C], NULL = none:
+ *   y[b,t,c] = mish(gn(x)[b,t,c]) * (t < len[b]) + add[b*ldadd + c] + res[b,t,c]
+ * summed in fp32 and rounded once.  res joins on EVERY frame, the bucket padding t >= *t_eff included (add does not): res
+ * holds what the caller wants there.  Both the one-launch and the two-launch paths honour res.  The backward is
+ * cvft_groupnorm_mish_bwd unchanged: the gradient of res is dy itself. */
+int cvft_groupnorm_mish_res_fwd(int dtype, int B, int T, int C, int G, const void* x, const float* gamma,
+                                const float* beta, float eps, const int32_t* len, const void* add, int ldadd,
+                                int apply_mish, const void* res, void* y, float* mean, float* rstd,
+                                const int32_t* t_eff, void* stream);
 int cvft_groupnorm_mish_bwd(int dtype, int B, int T, int C, int G, const void* x, const float* gamma,
                             const float* beta, const float* mean, const float* rstd, const int32_t* len,
                             int apply_mish, const void* dy, void* dx, float* ws /*[B*G*CVFT_GN_SPLIT*2] scratch*/,
