@@ -39,11 +39,12 @@ __device__ __forceinline__ void load_w8(const bf16_t* W, size_t off, float* w) {
 }
 
 // ---------------------------------------------------------------- decode linear
+// The main loop of both decode linears (plain and with the per-row LoRA epilogue term): the K-sum of output (m, n) of
+// this workgroup's DL_COLS columns, returned to thread t = c * MR + m (true when that thread owns a live output).
 template <typename WT, int MR>
-__global__ __launch_bounds__(DL_THREADS) void decode_linear_kernel(
+__device__ __forceinline__ bool decode_linear_dot(
     int M, int N, int K, const float* __restrict__ X, int ldx, const float* __restrict__ lg, const float* __restrict__ lb,
-    float eps, const WT* __restrict__ W, const float* __restrict__ bias, int act, const float* residual, int ldr, float* Y,
-    int ldy) {
+    float eps, const WT* __restrict__ W, int& m_out, int& n_out, float& y_out) {
     __shared__ float s_mean[MAX_LQ], s_rstd[MAX_LQ];
     __shared__ float s_red[DL_THREADS / WAVE][DL_COLS][MR];
     const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
@@ -117,11 +118,135 @@ __global__ __launch_bounds__(DL_THREADS) void decode_linear_kernel(
             float y = 0.f;
 #pragma unroll
             for (int w = 0; w < DL_THREADS / WAVE; ++w) y += s_red[w][c][m];
-            if (bias) y += bias[n];
-            if (act == 1) y = fmaxf(y, 0.f);
-            if (residual) y += residual[(size_t)m * ldr + n];
-            Y[(size_t)m * ldy + n] = y;
+            m_out = m; n_out = n; y_out = y;
+            return true;
         }
+    }
+    return false;
+}
+
+template <typename WT, int MR>
+__global__ __launch_bounds__(DL_THREADS) void decode_linear_kernel(
+    int M, int N, int K, const float* __restrict__ X, int ldx, const float* __restrict__ lg, const float* __restrict__ lb,
+    float eps, const WT* __restrict__ W, const float* __restrict__ bias, int act, const float* residual, int ldr, float* Y,
+    int ldy) {
+    int m, n;
+    float y;
+    if (!decode_linear_dot<WT, MR>(M, N, K, X, ldx, lg, lb, eps, W, m, n, y)) return;
+    if (bias) y += bias[n];
+    if (act == 1) y = fmaxf(y, 0.f);
+    if (residual) y += residual[(size_t)m * ldr + n];
+    Y[(size_t)m * ldy + n] = y;
+}
+
+// 8 consecutive adapter values as fp32.  The adapter stacks are a few MB re-read every step: plain loads, they stay cached.
+__device__ __forceinline__ void load_a8(const float* A, size_t off, float* w) {
+    const f32x4* p = reinterpret_cast<const f32x4*>(A + off);
+    f32x4 a = p[0], b = p[1];
+    w[0] = a[0]; w[1] = a[1]; w[2] = a[2]; w[3] = a[3]; w[4] = b[0]; w[5] = b[1]; w[6] = b[2]; w[7] = b[3];
+}
+__device__ __forceinline__ void load_a8(const bf16_t* A, size_t off, float* w) {
+    bf16x8 a = *reinterpret_cast<const bf16x8*>(A + off);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = (float)a[i];
+}
+
+// decode linear + the LoRA up-projection of the row's adapter: y = W.x + bias + scale[s] * Bst[s][n][:] . Z[m][g*R : g*R+R],
+// s = slot[m], g = n / Ng; then the activation, then the residual.  A row without a valid slot takes the plain epilogue.
+template <typename WT, int MR>
+__global__ __launch_bounds__(DL_THREADS) void decode_linear_lora_kernel(
+    int M, int N, int K, const float* __restrict__ X, int ldx, const float* __restrict__ lg, const float* __restrict__ lb,
+    float eps, const WT* __restrict__ W, const float* __restrict__ bias, int act, const float* residual, int ldr, float* Y,
+    int ldy, int S, int Ng, int R, const WT* __restrict__ Bst, const float* __restrict__ scale,
+    const int32_t* __restrict__ slot, const float* __restrict__ Z, int ldz) {
+    int m, n;
+    float y;
+    if (!decode_linear_dot<WT, MR>(M, N, K, X, ldx, lg, lb, eps, W, m, n, y)) return;
+    if (bias) y += bias[n];
+    const int s = slot[m];
+    if (s >= 0 && s < S) {
+        const float* z = Z + (size_t)m * ldz + (n / Ng) * R;
+        const size_t boff = ((size_t)s * N + n) * R;
+        float u = 0.f;
+        for (int j = 0; j < R; j += 8) {
+            float b[8];
+            load_a8(Bst, boff + j, b);
+            const f32x4 z0 = reinterpret_cast<const f32x4*>(z + j)[0], z1 = reinterpret_cast<const f32x4*>(z + j)[1];
+            const float zz[8] = {z0[0], z0[1], z0[2], z0[3], z1[0], z1[1], z1[2], z1[3]};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) u = fmaf(b[i], zz[i], u);
+        }
+        y += scale[s] * u;
+    }
+    if (act == 1) y = fmaxf(y, 0.f);
+    if (residual) y += residual[(size_t)m * ldr + n];
+    Y[(size_t)m * ldy + n] = y;
+}
+
+// LoRA down-projection of the decode rows: Z[m][g*R + j] = LN?(X)[m,:] . A[slot[m]][g][j][:].  One workgroup per
+// (8 values of j, group g, row m), so a row's result depends on nothing but that row; operands go straight to VGPRs.
+constexpr int LD_J = 8;
+template <typename WT>
+__global__ __launch_bounds__(DL_THREADS) void decode_lora_down_kernel(
+    int K, int S, int G, int R, const float* __restrict__ X, int ldx, const float* __restrict__ lg,
+    const float* __restrict__ lb, float eps, const WT* __restrict__ A, const int32_t* __restrict__ slot,
+    float* __restrict__ Z, int ldz) {
+    __shared__ float s_red[DL_THREADS / WAVE][LD_J];
+    const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
+    const int j0 = blockIdx.x * LD_J, g = blockIdx.y, m = blockIdx.z;
+    float* zo = Z + (size_t)m * ldz + g * R + j0;
+    const int s = slot[m];
+    if (s < 0 || s >= S) {      // no adapter: zeros, and the stack is never indexed
+        if (t < LD_J) zo[t] = 0.f;
+        return;
+    }
+    const float* x = X + (size_t)m * ldx;
+    const bool ln = lg != nullptr;
+    float mu = 0.f, rs = 1.f;
+    if (ln) {   // the two-pass row statistics of decode_linear_dot (every wave redoes them, in that order)
+        float sm = 0.f;
+        for (int k = lane; k < K; k += WAVE) sm += x[k];
+        mu = wave_sum(sm) / K;
+        float q = 0.f;
+        for (int k = lane; k < K; k += WAVE) { const float d = x[k] - mu; q += d * d; }
+        const float var = wave_sum(q) / K;
+        rs = 1.0f / sqrtf(var + eps);
+    }
+    const WT* a = A + (((size_t)s * G + g) * R + j0) * K;
+    float acc[LD_J];
+#pragma unroll
+    for (int j = 0; j < LD_J; ++j) acc[j] = 0.f;
+    const int NV = K / 8;
+    for (int v = t; v < NV; v += DL_THREADS) {
+        const int k = v * 8;
+        float xv[8];
+        load_a8(x, (size_t)k, xv);
+        if (ln) {
+            float gm[8], be[8];
+            load_a8(lg, (size_t)k, gm);
+            load_a8(lb, (size_t)k, be);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) xv[i] = (xv[i] - mu) * rs * gm[i] + be[i];
+        }
+#pragma unroll
+        for (int j = 0; j < LD_J; ++j) {
+            float w[8];
+            load_a8(a, (size_t)j * K + k, w);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[j] = fmaf(w[i], xv[i], acc[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < LD_J; ++j) {
+        const float r = wave_sum(acc[j]);
+        if (lane == 0) s_red[wv][j] = r;
+    }
+    __syncthreads();
+    if (t < LD_J) {
+        float z = 0.f;
+#pragma unroll
+        for (int w = 0; w < DL_THREADS / WAVE; ++w) z += s_red[w][t];
+        zo[t] = z;
     }
 }
 
@@ -133,6 +258,26 @@ int launch_linear(int M, int N, int K, const float* X, int ldx, const float* lg,
 #define DL_CASE(MR)                                                                                                  \
     hipLaunchKernelGGL((decode_linear_kernel<WT, MR>), grid, blk, 0, s, M, N, K, X, ldx, lg, lb, eps, w, bias, act, \
                        res, ldr, Y, ldy)
+    if (M <= 1) DL_CASE(1);
+    else if (M <= 2) DL_CASE(2);
+    else if (M <= 4) DL_CASE(4);
+    else if (M <= 8) DL_CASE(8);
+    else DL_CASE(16);
+#undef DL_CASE
+    return 0;
+}
+
+template <typename WT>
+int launch_linear_lora(int M, int N, int K, const float* X, int ldx, const float* lg, const float* lb, float eps,
+                       const void* W, const float* bias, int act, const float* res, int ldr, float* Y, int ldy, int S, int G,
+                       int R, const void* Bst, const float* scale, const int32_t* slot, const float* Z, int ldz,
+                       hipStream_t s) {
+    const dim3 grid((N + DL_COLS - 1) / DL_COLS), blk(DL_THREADS);
+    const WT* w = static_cast<const WT*>(W);
+    const WT* b = static_cast<const WT*>(Bst);
+#define DL_CASE(MR)                                                                                                       \
+    hipLaunchKernelGGL((decode_linear_lora_kernel<WT, MR>), grid, blk, 0, s, M, N, K, X, ldx, lg, lb, eps, w, bias, act, \
+                       res, ldr, Y, ldy, S, N / G, R, b, scale, slot, Z, ldz)
     if (M <= 1) DL_CASE(1);
     else if (M <= 2) DL_CASE(2);
     else if (M <= 4) DL_CASE(4);
@@ -465,6 +610,58 @@ extern "C" int cvft_decode_linear(int wdtype, int M, int N, int K, const float* 
     if (wdtype == 0) launch_linear<float>(M, N, K, X, ldx, ln_g, ln_b, ln_eps, W, bias, act, residual, ldr, Y, ldy, s);
     else launch_linear<bf16_t>(M, N, K, X, ldx, ln_g, ln_b, ln_eps, W, bias, act, residual, ldr, Y, ldy, s);
     CVFT_LAUNCH_CHECK("cvft_decode_linear");
+    return 0;
+}
+
+extern "C" int cvft_decode_lora_down(int wdtype, int M, int K, int S, int G, int R, const float* X, int ldx,
+                                     const float* ln_g, const float* ln_b, float ln_eps, const void* A,
+                                     const int32_t* slot, float* Z, int ldz, void* stream) {
+    CVFT_CHECK_ARG(M >= 1 && M <= MAX_LQ, "cvft_decode_lora_down: M=%d outside [1, 16]", M);
+    CVFT_CHECK_ARG(K >= 8 && K % 8 == 0 && S >= 1, "cvft_decode_lora_down: K=%d S=%d (K %% 8 == 0 required)", K, S);
+    CVFT_CHECK_ARG(G == 1 || G == 3, "cvft_decode_lora_down: G=%d (1 or 3)", G);
+    CVFT_CHECK_ARG(R == 8 || R == 16 || R == 32 || R == 64, "cvft_decode_lora_down: R=%d (8, 16, 32 or 64)", R);
+    CVFT_CHECK_ARG(X && A && slot && Z && ldx >= K && ldz >= G * R, "cvft_decode_lora_down: bad pointers / strides");
+    CVFT_CHECK_ARG(ldx % 4 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)A & 15) == 0,
+                   "cvft_decode_lora_down: X rows and A must be 16-byte aligned");
+    CVFT_CHECK_ARG(!ln_g == !ln_b, "cvft_decode_lora_down: ln_g and ln_b go together");
+    CVFT_CHECK_ARG(!ln_g || ((((uintptr_t)ln_g) | ((uintptr_t)ln_b)) & 15) == 0, "cvft_decode_lora_down: ln_g / ln_b alignment");
+    CVFT_CHECK_ARG(wdtype == 0 || wdtype == 1, "cvft_decode_lora_down: wdtype %d", wdtype);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(R / LD_J, G, M), blk(DL_THREADS);
+    if (wdtype == 0)
+        hipLaunchKernelGGL(decode_lora_down_kernel<float>, grid, blk, 0, s, K, S, G, R, X, ldx, ln_g, ln_b, ln_eps,
+                           static_cast<const float*>(A), slot, Z, ldz);
+    else
+        hipLaunchKernelGGL(decode_lora_down_kernel<bf16_t>, grid, blk, 0, s, K, S, G, R, X, ldx, ln_g, ln_b, ln_eps,
+                           static_cast<const bf16_t*>(A), slot, Z, ldz);
+    CVFT_LAUNCH_CHECK("cvft_decode_lora_down");
+    return 0;
+}
+
+extern "C" int cvft_decode_linear_lora(int wdtype, int M, int N, int K, const float* X, int ldx, const float* ln_g,
+                                       const float* ln_b, float ln_eps, const void* W, const float* bias, int act,
+                                       const float* residual, int ldr, float* Y, int ldy, int S, int G, int R,
+                                       const void* Bst, const float* scale, const int32_t* slot, const float* Z, int ldz,
+                                       void* stream) {
+    CVFT_CHECK_ARG(M >= 1 && M <= MAX_LQ, "cvft_decode_linear_lora: M=%d outside [1, 16]", M);
+    CVFT_CHECK_ARG(N >= 1 && K >= 8 && K % 8 == 0, "cvft_decode_linear_lora: N=%d K=%d (K %% 8 == 0 required)", N, K);
+    CVFT_CHECK_ARG(X && W && Y && ldx >= K && ldy >= N && (!residual || ldr >= N), "cvft_decode_linear_lora: bad pointers / strides");
+    CVFT_CHECK_ARG(ldx % 4 == 0 && ((uintptr_t)X & 15) == 0, "cvft_decode_linear_lora: X rows must be 16-byte aligned");
+    CVFT_CHECK_ARG(!ln_g == !ln_b, "cvft_decode_linear_lora: ln_g and ln_b go together");
+    CVFT_CHECK_ARG(act == 0 || act == 1, "cvft_decode_linear_lora: act %d (0 none, 1 relu)", act);
+    CVFT_CHECK_ARG(wdtype == 0 || wdtype == 1, "cvft_decode_linear_lora: wdtype %d", wdtype);
+    CVFT_CHECK_ARG(S >= 1 && (G == 1 || G == 3) && N % G == 0, "cvft_decode_linear_lora: S=%d G=%d N=%d (G 1 or 3, N %% G == 0)", S, G, N);
+    CVFT_CHECK_ARG(R == 8 || R == 16 || R == 32 || R == 64, "cvft_decode_linear_lora: R=%d (8, 16, 32 or 64)", R);
+    CVFT_CHECK_ARG(Bst && scale && slot && Z && ldz >= G * R && ldz % 4 == 0 && ((uintptr_t)Z & 15) == 0 &&
+                       ((uintptr_t)Bst & 15) == 0, "cvft_decode_linear_lora: bad adapter pointers / strides");
+    hipStream_t s = (hipStream_t)stream;
+    if (wdtype == 0)
+        launch_linear_lora<float>(M, N, K, X, ldx, ln_g, ln_b, ln_eps, W, bias, act, residual, ldr, Y, ldy, S, G, R, Bst,
+                                  scale, slot, Z, ldz, s);
+    else
+        launch_linear_lora<bf16_t>(M, N, K, X, ldx, ln_g, ln_b, ln_eps, W, bias, act, residual, ldr, Y, ldy, S, G, R, Bst,
+                                   scale, slot, Z, ldz, s);
+    CVFT_LAUNCH_CHECK("cvft_decode_linear_lora");
     return 0;
 }
 

@@ -47,6 +47,46 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
     return out
 
 
+def decode_lora_down(x: torch.Tensor, A: torch.Tensor, slot: torch.Tensor, ln=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [M <= 16, K] fp32, A [S, G, R, K] fp32 | bf16 (the adapters' lora_A, stacked), slot [M] int32 (device)
+    -> z [M, G*R] fp32: LN?(x) against each row's own adapter; rows whose slot is outside [0, S) get zeros."""
+    M, K = x.shape
+    S, G, R = A.shape[:3]
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and A.is_contiguous() and A.shape[3] == K
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.numel() >= M
+    if out is None:
+        out = torch.empty((M, G * R), dtype=torch.float32, device=x.device)
+    g, b, eps = ln if ln is not None else (None, None, 0.0)
+    check(lib().cvft_decode_lora_down(F32 if A.dtype == torch.float32 else BF16, M, K, S, G, R, ptr(x), x.stride(0), ptr(g),
+                                      ptr(b), float(eps), ptr(A), ptr(slot), ptr(out), out.stride(0), stream()),
+          "cvft_decode_lora_down")
+    return out
+
+
+def decode_linear_lora(x: torch.Tensor, w: torch.Tensor, Bst: torch.Tensor, scale: torch.Tensor, slot: torch.Tensor,
+                       z: torch.Tensor, G: int = 1, bias: Optional[torch.Tensor] = None, ln=None, act: int = 0,
+                       residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """decode_linear plus each row's adapter: act(LN?(x) w^T + bias + scale[s] * Bst[s] z_g) (+ residual), s = slot[m],
+    z [M, >= G*R] from decode_lora_down, Bst [S, N, R] in w's dtype, scale [S] fp32.  Rows without adapter: decode_linear."""
+    M, K = x.shape
+    N = w.shape[0]
+    S, _, R = Bst.shape
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and w.is_contiguous() and w.shape[1] == K
+    assert Bst.is_contiguous() and Bst.shape[1] == N and Bst.dtype == w.dtype and scale.numel() == S
+    assert scale.dtype == torch.float32 and slot.dtype == torch.int32 and slot.numel() >= M
+    assert z.dtype == torch.float32 and z.stride(1) == 1 and z.shape[0] >= M and z.shape[1] >= G * R
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    g, b, eps = ln if ln is not None else (None, None, 0.0)
+    check(lib().cvft_decode_linear_lora(F32 if w.dtype == torch.float32 else BF16, M, N, K, ptr(x), x.stride(0), ptr(g),
+                                        ptr(b), float(eps), ptr(w), ptr(bias), act, ptr(residual),
+                                        residual.stride(0) if residual is not None else 0, ptr(out), out.stride(0), S, G, R,
+                                        ptr(Bst), ptr(scale), ptr(slot), ptr(z), z.stride(0), stream()),
+          "cvft_decode_linear_lora")
+    return out
+
+
 def decode_attn(qkv, kc, vc, length, P, pos_bias_u, pos_bias_v, B: int, H: int, Lq: int, done=None, part=None,
                 out=None) -> torch.Tensor:
     """qkv [B*Lq, >= 3*H*64] (q | k | v of the new rows), kc / vc [B, H, cap, 64] fp32 (appended in place at length[b]),
@@ -81,6 +121,16 @@ def merged_weight(mod, wdtype):
     return W.to(wdtype).contiguous(), (b.detach().float().contiguous() if b is not None else None)
 
 
+def base_weight(mod, wdtype):
+    """(W, bias) like merged_weight but of the frozen layer alone: the unfolded pack an AdapterBank decodes against."""
+    _, w, b, _, _, _, _ = _lin_parts(mod)
+    return w.detach().to(wdtype).contiguous(), (b.detach().float().contiguous() if b is not None else None)
+
+
+def lora_wrapped(mod) -> bool:
+    return _lin_parts(mod)[3] is not None
+
+
 def rel_pos_table(d: int, n: int) -> torch.Tensor:
     """pe rows for the relative distances 0 .. n-1 (the positive half of EspnetRelPositionalEncoding's table)."""
     pos = torch.arange(0, n, dtype=torch.float32).unsqueeze(1)
@@ -98,15 +148,20 @@ def bucket(n: int) -> int:
 class PackedStack:
     """The weights of a RelPosEncoder (input layer + pre-norm layers + after_norm) packed once for the decode kernels:
     merged linears in `wdtype`, LayerNorm / positional-bias parameters fp32.  Shared by every DecodeStack (batch size,
-    capacity bucket) built from it."""
+    capacity bucket) built from it.  fold=False packs W alone (the unfolded form: the adapters come per row from an
+    AdapterBank's stacks, so the pack depends on no ``lora_`` parameter)."""
 
-    def __init__(self, enc, wdtype: torch.dtype, xscale: bool = True):
+    def __init__(self, enc, wdtype: torch.dtype, xscale: bool = True, fold: bool = True):
+        self.folded = fold
+        if not fold and lora_wrapped(enc.embed.out[0]):
+            raise NotImplementedError("unfolded decode: a LoRA-wrapped input layer is not built")
+        weight = merged_weight if fold else base_weight
         dev = enc.after_norm.weight.device
         f32 = lambda t: t.detach().float().contiguous()       # noqa: E731
         self.d = d = enc.output_size()
         self.dev = dev
         e0, e1 = enc.embed.out[0], enc.embed.out[1]
-        self.W_emb, self.b_emb = merged_weight(e0, wdtype)
+        self.W_emb, self.b_emb = weight(e0, wdtype)
         self.ln_emb = (f32(e1.weight), f32(e1.bias), e1.eps)
         self.emb_relu, self.emb_scale = enc.embed.legacy, (math.sqrt(d) if xscale else 1.0)
         self.after = (f32(enc.after_norm.weight), f32(enc.after_norm.bias), enc.after_norm.eps)
@@ -116,11 +171,11 @@ class PackedStack:
             if ff.activation != "relu":
                 raise NotImplementedError("decode is built for the TransformerEncoder (ReLU feed-forward) stack")
             n1, n2 = (layer.norm_mha, layer.norm_ff) if layer.conformer else (layer.norm1, layer.norm2)
-            ws = [merged_weight(m, wdtype) for m in (at.linear_q, at.linear_k, at.linear_v)]
+            ws = [weight(m, wdtype) for m in (at.linear_q, at.linear_k, at.linear_v)]
             bq = [b if b is not None else torch.zeros(d, device=dev) for _, b in ws]
-            Wo, bo = merged_weight(at.linear_out, wdtype)
-            W1, b1 = merged_weight(ff.w_1, wdtype)
-            W2, b2 = merged_weight(ff.w_2, wdtype)
+            Wo, bo = weight(at.linear_out, wdtype)
+            W1, b1 = weight(ff.w_1, wdtype)
+            W2, b2 = weight(ff.w_2, wdtype)
             self.layers.append(dict(
                 Wqkv=torch.cat([w for w, _ in ws]).contiguous(), bqkv=torch.cat(bq).contiguous(),
                 ln1=(f32(n1.weight), f32(n1.bias), n1.eps), ln2=(f32(n2.weight), f32(n2.bias), n2.eps),
@@ -159,6 +214,7 @@ class DecodeStack:
         self.h, self.qkv, self.o, self.f, self.e = z(R, d), z(R, 3 * d), z(R, d), z(R, self.F), z(R, d)
         self.mean, self.rstd = z(R), z(R)
         self.part = z(R * self.H * (-(-cap // ATT_KEYS)) * 66)
+        self.z = None             # [R, 3 * bank rank]: the adapters' down-projections (sessions over an AdapterBank)
 
     def embed(self, xin: torch.Tensor, M: int) -> torch.Tensor:
         """input layer (Linear -> LayerNorm (-> ReLU) -> x sqrt(d)) of M rows into self.h[:M]."""
@@ -166,13 +222,17 @@ class DecodeStack:
         g, b, eps = self.ln_emb
         return _layernorm(self.e[:M], g, b, eps, self.h[:M], self.mean, self.rstd, self.emb_relu, self.emb_scale)
 
-    def layers_fwd(self, B: int, Lq: int, row: Optional[int] = None):
-        """the layers over self.h[:B*Lq] (Lq new rows per sequence).  row: a single cache row (prefill of one request)."""
+    def layers_fwd(self, B: int, Lq: int, row: Optional[int] = None, lora=None):
+        """the layers over self.h[:B*Lq] (Lq new rows per sequence).  row: a single cache row (prefill of one request).
+        lora = (an AdapterBank's per-layer stacks, slot [>= B*Lq] int32): every linear becomes down -> linear_lora with
+        each row's own adapter (the pack is then the unfolded one)."""
         M = B * Lq
         h = self.h[:M]
         sl = slice(None) if row is None else slice(row, row + 1)
         length = self.len[sl]
         done = self.done[sl]
+        if lora is not None:
+            return self._layers_fwd_lora(B, Lq, h, sl, length, done, *lora)
         for i, L in enumerate(self.layers):
             qkv = decode_linear(h, L["Wqkv"], L["bqkv"], ln=L["ln1"], out=self.qkv[:M])
             o = decode_attn(qkv, self.kc[i, sl], self.vc[i, sl], length, self.P[i], L["u"], L["v"], B, self.H, Lq, done=done,
@@ -180,6 +240,22 @@ class DecodeStack:
             decode_linear(o, L["Wo"], L["bo"], residual=h, out=h)
             f = decode_linear(h, L["W1"], L["b1"], ln=L["ln2"], act=1, out=self.f[:M])
             decode_linear(f, L["W2"], L["b2"], residual=h, out=h)
+        return h
+
+    def _layers_fwd_lora(self, B, Lq, h, sl, length, done, bank, slot):
+        M = B * Lq
+        z, sc = self.z, bank.scale
+        for i, (L, A) in enumerate(zip(self.layers, bank.layers)):
+            decode_lora_down(h, A["A_qkv"], slot, ln=L["ln1"], out=z[:M])
+            qkv = decode_linear_lora(h, L["Wqkv"], A["B_qkv"], sc, slot, z, 3, L["bqkv"], ln=L["ln1"], out=self.qkv[:M])
+            o = decode_attn(qkv, self.kc[i, sl], self.vc[i, sl], length, self.P[i], L["u"], L["v"], B, self.H, Lq, done=done,
+                            part=self.part, out=self.o[:M])
+            decode_lora_down(o, A["A_o"], slot, out=z[:M])
+            decode_linear_lora(o, L["Wo"], A["B_o"], sc, slot, z, 1, L["bo"], residual=h, out=h)
+            decode_lora_down(h, A["A_1"], slot, ln=L["ln2"], out=z[:M])
+            f = decode_linear_lora(h, L["W1"], A["B_1"], sc, slot, z, 1, L["b1"], ln=L["ln2"], act=1, out=self.f[:M])
+            decode_lora_down(f, A["A_2"], slot, out=z[:M])
+            decode_linear_lora(f, L["W2"], A["B_2"], sc, slot, z, 1, L["b2"], residual=h, out=h)
         return h
 
     def prefill(self, x: torch.Tensor, row: int = 0) -> torch.Tensor:
@@ -242,12 +318,16 @@ class SamplerCfg:
 
 
 class PackedLM:
-    """The weights of a TransformerLM's decode path, packed once per weight dtype (PackedStack + decoder + table)."""
+    """The weights of a TransformerLM's decode path, packed once per weight dtype (PackedStack + decoder + table).
+    fold=False: W only, for sessions that take their adapters per row from an AdapterBank."""
 
-    def __init__(self, lm):
+    def __init__(self, lm, fold: bool = True):
         self.wdtype = torch.bfloat16 if lm.numerics.dtype == torch.bfloat16 else torch.float32
-        self.stack = PackedStack(lm.llm, self.wdtype, xscale=lm.numerics.xscale)
-        self.W_dec, self.b_dec = merged_weight(lm.llm_decoder, self.wdtype)
+        self.folded = fold
+        if not fold and lora_wrapped(lm.llm_decoder):
+            raise NotImplementedError("unfolded decode: a LoRA-wrapped llm_decoder is not built")
+        self.stack = PackedStack(lm.llm, self.wdtype, xscale=lm.numerics.xscale, fold=fold)
+        self.W_dec, self.b_dec = (merged_weight if fold else base_weight)(lm.llm_decoder, self.wdtype)
         self.table = lm.speech_embedding.weight.detach().float().contiguous()
         self.eos = lm.speech_token_size
         self.d_in = lm.llm_input_size
@@ -256,11 +336,19 @@ class PackedLM:
 class LMDecodeSession:
     """B rows of lockstep decode of a TransformerLM (see the module docstring) over shared packed weights."""
 
-    def __init__(self, packed: PackedLM, B: int, cap: int):
+    def __init__(self, packed: PackedLM, B: int, cap: int, bank=None):
+        """bank: an adapters.AdapterBank's stacks for packed.wdtype (the pack is then the unfolded one): every row decodes
+        with the adapter whose slot stands in self.slot (-1: none); the captured step holds the stacks' fixed addresses."""
         dev = packed.stack.dev
         self.wdtype = packed.wdtype
+        assert (bank is None) == packed.folded, "a folded pack decodes without a bank, an unfolded one with one"
+        self.bank = bank
+        self.slot = torch.full((max(B, MAX_ROWS),), -1, dtype=torch.int32, device=dev)      # per decode row
+        self.pslot = torch.full((MAX_ROWS,), -1, dtype=torch.int32, device=dev)             # the request being prefilled
         self.B, self.cap, self.dev = B, cap, dev
         self.stack = DecodeStack(packed.stack, cap, B)
+        if bank is not None:
+            self.stack.z = torch.zeros((self.stack.h.shape[0], 3 * bank.rank), dtype=torch.float32, device=dev)
         self.W_dec, self.b_dec, self.table, self.eos = packed.W_dec, packed.b_dec, packed.table, packed.eos
         self.V = self.W_dec.shape[0]
         i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)   # noqa: E731
@@ -298,16 +386,21 @@ class LMDecodeSession:
         check(lib().cvft_gather_rows(F32, B, self.table.shape[1], ptr(self.next_in), ptr(self.table), 0.0, ptr(self.xin),
                                      stream()), "cvft_gather_rows")
         st.embed(self.xin[:B], B)
-        h = st.layers_fwd(B, 1)
+        h = st.layers_fwd(B, 1, lora=None if self.bank is None else (self.bank, self.slot))
         decode_linear(h, self.W_dec, self.b_dec, ln=st.after, out=self.logits)
         self._sample(bump_len=self.cfg.mode != "logp")
 
     # ---- driving
     def start(self, rows: List[torch.Tensor], min_len: Sequence[int], max_len: Sequence[int], seeds: Sequence[int],
-              cfg: SamplerCfg, uniforms: Optional[torch.Tensor] = None):
-        """prefill every request's lm_input rows into its cache row and draw its first token."""
+              cfg: SamplerCfg, uniforms: Optional[torch.Tensor] = None, slots: Optional[Sequence[int]] = None):
+        """prefill every request's lm_input rows into its cache row and draw its first token.  slots (sessions over an
+        AdapterBank): each request's adapter slot, -1 for none."""
         st = self.stack
         assert len(rows) == self.B
+        assert (slots is not None) == (self.bank is not None), "slots go with a bank session"
+        if slots is not None:
+            self.slots = [int(v) for v in slots]
+            self.slot[:self.B].copy_(torch.tensor(self.slots, dtype=torch.int32))
         self.cfg = cfg
         if uniforms is not None:              # copied into the session's own buffer: a captured step keeps its address
             self.ubuf.copy_(uniforms.reshape(self.B, TRIALS, 2))
@@ -331,7 +424,11 @@ class LMDecodeSession:
         for c0 in range(0, T, MAX_ROWS):
             n = min(MAX_ROWS, T - c0)
             st.embed(x[c0:c0 + n].float().contiguous(), n)
-            h = st.layers_fwd(1, n, row=b)
+            if self.bank is None:
+                h = st.layers_fwd(1, n, row=b)
+            else:
+                self.pslot.fill_(self.slots[b])
+                h = st.layers_fwd(1, n, row=b, lora=(self.bank, self.pslot))
             st.len[b].fill_(c0 + n)
         self._decoder_logits(h, [n - 1], [b])
 

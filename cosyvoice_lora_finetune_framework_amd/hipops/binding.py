@@ -190,6 +190,9 @@ SIGNATURES = {
     "cvft_block_link_bwd": [C.POINTER(BlockQkvBwdArgs), C.POINTER(BlockTailBwdArgs), _p, _p],
     "cvft_block_qkv_bwd": [C.POINTER(BlockQkvBwdArgs), _p],
     "cvft_decode_linear": [_i, _i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _i, _p, _i, _p, _i, _p],
+    "cvft_decode_lora_down": [_i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _p, _i, _p],
+    "cvft_decode_linear_lora": [_i, _i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p,
+                                _i, _p],
     "cvft_decode_attn": [_i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _f, _p, _p, _i, _p],
     "cvft_decode_sample": [_i, _i, _p, _i, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
                            _p],

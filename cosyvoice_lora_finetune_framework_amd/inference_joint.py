@@ -9,6 +9,7 @@ without the text front-end.
         [--prompt-wav p.wav --prompt-tokens 5,9,.. --prompt-text-tokens 3,4,.. --embedding e.npy]
         [--speech-tokenizer speech_tokenizer_v1.onnx] [--campplus campplus.onnx]
         [--stream [--token-hop 100]]
+        [--lora NAME=PATH ... --voice NAME [--llm-lora-config '{...}' --flow-lora-config '{...}']]
 
 ``--llm`` / ``--flow`` are the merged state_dicts ``merge_joint_weights.py`` writes; ``--text-tokens`` is a comma-separated
 id list or a ``.npy`` file of ids.  The mel is de-normalised with MEL_MEAN / MEL_STD and written as [80, T] float32.
@@ -31,6 +32,11 @@ An explicit ``--prompt-tokens`` or ``--embedding`` still wins.
 the reference's ``tts(stream=True)``): each chunk is appended to ``--wav`` as it arrives, the time to the first chunk and
 the total time are printed and no mel file is written.  ``--token-hop`` is the number of new speech tokens per chunk
 (default 2 x the Flow's token rate).  ``--wav-rate`` must stay 22050 with it: the resampler keeps no state between chunks.
+``--lora NAME=PATH`` (repeatable; a name may come twice, one file per branch) serves fine-tuned voices without merging:
+``--llm`` / ``--flow`` are then the BASE weights in the original key names, their target layers are LoRA-wrapped as
+``--llm-lora-config`` / ``--flow-lora-config`` say (JSON ``{lora_r, lora_alpha, target_modules}``; default config.py's
+``llm_lora`` / ``flow_lora``), every PATH (a ``save_lora_weights`` file or a trainer checkpoint) stays resident in an
+``adapters.AdapterBank`` and ``--voice NAME`` picks the one to synthesise with (without it: the base models).
 """
 from __future__ import annotations
 
@@ -53,7 +59,7 @@ from .config import MEL_MEAN, MEL_STD
 def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] = None,
                noise: Optional[torch.Tensor] = None, *, prompt_wav: Optional[torch.Tensor] = None,
                prompt_speech_token=None, prompt_text=None, embedding: Optional[torch.Tensor] = None,
-               prompt_rate: Optional[int] = None, frontend=None) -> Tuple[List[int], torch.Tensor]:
+               prompt_rate: Optional[int] = None, frontend=None, adapter=None) -> Tuple[List[int], torch.Tensor]:
     """-> (speech tokens, de-normalised mel (1, 80, T) fp32).  `seed` pins the LLM's sampler, `noise` the Flow's
     initial z.  Zero-shot prompting: `prompt_wav` (samples at 22 050 Hz, or at `prompt_rate` Hz: then it is resampled to
     22 050 Hz first, audio.Resampler) becomes the Flow's `prompt_feat` -- its log-mel
@@ -61,8 +67,12 @@ def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] =
     non-empty prompt --, `prompt_speech_token` goes to both models, `prompt_text` to the LLM, `embedding` (1, 192) to
     both.  With none of them the prompt is empty and the embedding zero.  `frontend` (frontend16k.SpeechFrontend) fills
     what `prompt_wav` comes without: `prompt_speech_token` from its speech tokenizer, `embedding` from its speaker
-    encoder, both on the prompt resampled to 16 kHz; a value passed explicitly wins."""
+    encoder, both on the prompt resampled to 16 kHz; a value passed explicitly wins.  `adapter`: a voice resident in the
+    models' adapters.AdapterBank (or adapters.BASE): `llm` and `flow` then hold the base weights and run with that
+    adapter; None runs the models as they are."""
     dev = llm.llm_decoder.weight.device
+    if adapter is not None:
+        activate_adapter(llm, flow, adapter)
     if frontend is not None and prompt_wav is not None:
         prompt_speech_token, embedding = prompt_from_wav(frontend, prompt_wav, prompt_rate, dev, prompt_speech_token, embedding)
     text = torch.as_tensor(text_tokens, dtype=torch.long).reshape(1, -1).to(dev)
@@ -80,7 +90,7 @@ def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] =
             p_wav, _ = resample(p_wav, prompt_rate, SAMPLE_RATE)
         p_feat = (extractor(dev)(p_wav, channel_last=True) - MEL_MEAN) / MEL_STD
     n = lambda t: torch.tensor([t.shape[1]])                                                           # noqa: E731
-    tokens = list(llm.inference(text, n(text), p_text, n(p_text), p_tok, n(p_tok), emb, seed=seed))
+    tokens = list(llm.inference(text, n(text), p_text, n(p_text), p_tok, n(p_tok), emb, seed=seed, adapter=adapter))
     if not tokens:
         raise RuntimeError("the LLM produced no speech tokens")
     tok = torch.tensor([tokens], dtype=torch.long, device=dev)
@@ -89,6 +99,40 @@ def synthesize(llm, flow, text_tokens, speed: float = 1.0, seed: Optional[int] =
     if speed != 1.0:
         mel = F.interpolate(mel, size=int(mel.shape[2] / speed), mode='linear')
     return tokens, mel
+
+
+def activate_adapter(llm, flow, adapter) -> None:
+    """set the module-run LoRA layers of both models to `adapter` (on the current stream, before either model runs)."""
+    from .adapters import bank_of
+    banks = [bank_of(llm)] + ([flow.__dict__["_cvft_adapter_bank"]] if "_cvft_adapter_bank" in flow.__dict__ else [])
+    for bank in {id(b): b for b in banks}.values():
+        bank.activate(adapter)
+
+
+def load_adapters(llm, flow, specs: List[str], llm_lora: dict, flow_lora: dict, rank: Optional[int] = None):
+    """--lora NAME=PATH ...: wrap the base models' target layers (zero adapters), build one AdapterBank over both and
+    load every file into its name (one file per branch, or a trainer checkpoint: a name may be given more than once)."""
+    from .adapters import RANKS, AdapterBank
+    from .lora import apply_lora_to_model
+    for model, cfg in ((llm, llm_lora), (flow, flow_lora)):
+        apply_lora_to_model(model, r=cfg['lora_r'], lora_alpha=cfg['lora_alpha'], lora_dropout=0.0,
+                            target_modules=cfg['target_modules'])
+        for n, p in model.named_parameters():
+            if 'lora_' in n:
+                p.data.zero_()
+    pairs = []
+    for spec in specs:
+        name, sep, path = spec.partition('=')
+        if not sep or not name or not path:
+            raise SystemExit(f"--lora wants NAME=PATH, got '{spec}'")
+        pairs.append((name, path))
+    names = list(dict.fromkeys(n for n, _ in pairs))
+    if rank is None:
+        rank = next(r for r in RANKS if r >= max(llm_lora['lora_r'], 8))
+    bank = AdapterBank(llm=llm, flow=flow, capacity=max(len(names), 1), rank=rank)
+    for name, path in pairs:
+        bank.load(name, path)
+    return bank
 
 
 def prompt_from_wav(frontend, prompt_wav: torch.Tensor, prompt_rate: Optional[int], dev, prompt_speech_token=None,
@@ -139,8 +183,14 @@ def main(argv=None):
     from .llm_model import build_llm_model
     from .modules import Numerics
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
-    ap.add_argument('--llm', required=True, help='merged LLM state_dict (merge_joint_weights.py)')
-    ap.add_argument('--flow', required=True, help='merged Flow state_dict (merge_joint_weights.py)')
+    ap.add_argument('--llm', required=True, help='merged LLM state_dict (merge_joint_weights.py); with --lora: the base LLM')
+    ap.add_argument('--flow', required=True, help='merged Flow state_dict (merge_joint_weights.py); with --lora: the base Flow')
+    ap.add_argument('--lora', action='append', default=[], metavar='NAME=PATH',
+                    help='a voice: LoRA tensors (save_lora_weights file of a branch, or a trainer checkpoint) kept resident '
+                         'under NAME over the base models; repeatable, also per name')
+    ap.add_argument('--voice', default=None, help='with --lora: the NAME to synthesise with (default: the base models)')
+    ap.add_argument('--llm-lora-config', default=None, help='JSON {lora_r, lora_alpha, target_modules} (default: config.py llm_lora)')
+    ap.add_argument('--flow-lora-config', default=None, help='JSON {lora_r, lora_alpha, target_modules} (default: config.py flow_lora)')
     ap.add_argument('--text-tokens', required=True, help='comma-separated text token ids, or a .npy file of ids')
     ap.add_argument('--out', default='mel.npy')
     ap.add_argument('--speed', type=float, default=1.0)
@@ -176,6 +226,8 @@ def main(argv=None):
         ap.error('--noise pins one initial noise tensor; with --stream every chunk draws its own (use --seed / torch.manual_seed)')
     if a.token_hop is not None and not a.stream:
         ap.error('--token-hop is an option of --stream')
+    if a.voice is not None and not a.lora:
+        ap.error('--voice names one of the --lora NAME=PATH adapters')
     num = Numerics(dtype=torch.bfloat16 if a.dtype == 'bf16' else torch.float32)
     kw = lambda js: {k: tuple(v) if isinstance(v, list) else v for k, v in json.loads(js).items()}   # noqa: E731
     llm = build_llm_model(None, 'cpu', numerics=num, **kw(a.llm_config))
@@ -184,6 +236,14 @@ def main(argv=None):
     flow.load_state_dict(torch.load(a.flow, map_location='cpu', weights_only=True), strict=True)
     dev = torch.device('cuda')
     llm, flow = llm.to(dev).eval(), flow.to(dev).eval()
+    adapter = None
+    if a.lora:
+        from .adapters import BASE
+        from .config import JOINT_TRAINING_CONFIG
+        cfgs = [json.loads(js) if js else JOINT_TRAINING_CONFIG[k]
+                for js, k in ((a.llm_lora_config, 'llm_lora'), (a.flow_lora_config, 'flow_lora'))]
+        load_adapters(llm, flow, a.lora, *cfgs)
+        adapter = a.voice if a.voice is not None else BASE
     llm.sampling = functools.partial(U.ras_sampling, top_p=a.top_p, top_k=a.top_k, win_size=a.win_size, tau_r=a.tau_r)
     noise = torch.from_numpy(np.load(a.noise)).float().to(dev) if a.noise else None
     prompt = {}
@@ -206,8 +266,8 @@ def main(argv=None):
         if emb is not None:
             prompt['embedding'] = emb
     if a.stream:
-        return _stream_main(a, llm, flow, dev, prompt)
-    tokens, mel = synthesize(llm, flow, _text_tokens(a.text_tokens), a.speed, a.seed, noise=noise, **prompt)
+        return _stream_main(a, llm, flow, dev, prompt, adapter)
+    tokens, mel = synthesize(llm, flow, _text_tokens(a.text_tokens), a.speed, a.seed, noise=noise, adapter=adapter, **prompt)
     np.save(a.out, mel[0].cpu().numpy().astype(np.float32))
     print(f"{len(tokens)} speech tokens -> mel {tuple(mel.shape[1:])} -> {a.out}")
     if a.hift:
@@ -222,7 +282,7 @@ def main(argv=None):
         print(f"mel -> {wav.shape[1]} samples at {a.wav_rate} Hz -> {a.wav}")
 
 
-def _stream_main(a, llm, flow, dev, prompt):
+def _stream_main(a, llm, flow, dev, prompt, adapter=None):
     """--stream: chunks go to --wav as they arrive (16-bit PCM converted on the device by the stitch launch)."""
     import time
     from .hift import HiFTGenerator
@@ -239,7 +299,7 @@ def _stream_main(a, llm, flow, dev, prompt):
         f.setsampwidth(2)
         f.setframerate(voc.sampling_rate)
         for item in syn.tts(_text_tokens(a.text_tokens), stream=True, seed=a.seed, hift_seed=a.hift_seed,
-                            want_pcm=True, **prompt):
+                            want_pcm=True, adapter=adapter, **prompt):
             pcm = item['pcm'].cpu().numpy().astype('<i2')
             first = time.perf_counter() - t0 if first is None else first
             f.writeframes(pcm.tobytes())

@@ -186,24 +186,30 @@ class TransformerLM(nn.Module):
 
     MAX_SESSIONS = 4
 
-    def decode_session(self, B: int, cap: int) -> "DEC.LMDecodeSession":
+    def decode_session(self, B: int, cap: int, bank=None) -> "DEC.LMDecodeSession":
         """The weights are packed once per weight dtype (rebuilt when a parameter changes) and shared by the sessions;
         sessions (K/V caches, positional tables, captured step) are kept per (batch, capacity bucket, dtype), the
-        MAX_SESSIONS most recently used ones."""
+        MAX_SESSIONS most recently used ones.  bank (adapters.AdapterBank): the unfolded pack (W alone, rebuilt only when
+        a parameter other than the ``lora_`` ones changes) and sessions that read each row's adapter from the bank's
+        stacks -- loading, evicting or activating adapters leaves both, and their captured steps, as they are."""
         cap = DEC.bucket(cap)
-        ver = tuple(p._version for p in self.parameters())
+        fold = bank is None
+        ver = tuple(p._version for n, p in self.named_parameters() if fold or 'lora_' not in n)
         dtype = self.numerics.dtype
         packs = self.__dict__.setdefault("_cvft_decode_weights", {})
         sessions = self.__dict__.setdefault("_cvft_sessions", collections.OrderedDict())
-        pk = packs.get(dtype)
+        pkey = dtype if fold else (dtype, "unfolded")
+        tag = None if fold else id(bank)
+        pk = packs.get(pkey)
         if pk is None or pk[0] != ver:
-            for k in [k for k in sessions if k[2] == dtype]:
+            for k in [k for k in sessions if k[2] == dtype and (len(k) == 3) == fold]:
                 del sessions[k]
-            packs[dtype] = pk = (ver, DEC.PackedLM(self))
-        key = (B, cap, dtype)
+            packs[pkey] = pk = (ver, DEC.PackedLM(self, fold=fold))
+        key = (B, cap, dtype) if fold else (B, cap, dtype, tag)
         hit = sessions.get(key)
         if hit is None:
-            hit = sessions[key] = (ver, DEC.LMDecodeSession(pk[1], B, cap))
+            stacks = None if fold else bank.stacks(pk[1].wdtype)
+            hit = sessions[key] = (ver, DEC.LMDecodeSession(pk[1], B, cap, bank=stacks))
             while len(sessions) > self.MAX_SESSIONS:
                 sessions.popitem(last=False)
         sessions.move_to_end(key)
@@ -218,23 +224,26 @@ class TransformerLM(nn.Module):
                   prompt_text_len: torch.Tensor, prompt_speech_token: torch.Tensor, prompt_speech_token_len: torch.Tensor,
                   embedding: torch.Tensor, sampling: int = 25, max_token_text_ratio: float = 20,
                   min_token_text_ratio: float = 2, uuid: str = '', use_graph: bool = True, seed: Optional[int] = None,
-                  uniforms: Optional[torch.Tensor] = None) -> Generator[int, None, None]:
+                  uniforms: Optional[torch.Tensor] = None, adapter=None) -> Generator[int, None, None]:
         """llm.py:165-228: yields speech-token ids until EOS (not yielded) or max_len.  `text_len` counts the text
         WITHOUT the prompt (the reference adds prompt_text_len).  Extra keywords: use_graph=False runs the same
         kernels without capture; seed / uniforms pin the sampler's draws (default: one seed per request drawn from
-        torch's generator)."""
+        torch's generator).  adapter: None decodes the module's own (merged) weights; a name resident in the model's
+        adapters.AdapterBank, or adapters.BASE, decodes the base weights with that adapter (the text encoder's LoRA
+        parameters are set to it first).  The adapter must stay resident until the generator ends."""
+        bank, slots = self._adapter_slots([adapter]) if adapter is not None else (None, None)
         rows, n_text = self.lm_input_rows(text, text_len, prompt_text, prompt_text_len, prompt_speech_token,
                                           prompt_speech_token_len, embedding)
         min_len, max_len = int(n_text * min_token_text_ratio), int(n_text * max_token_text_ratio)
         if max_len <= 0:
             return
         cfg = self.sampler_cfg()
-        sess = self.decode_session(1, rows.shape[0] + max_len)
+        sess = self.decode_session(1, rows.shape[0] + max_len, bank=bank)
         if cfg is None:
-            yield from self._inference_host(sess, rows, min_len, max_len, sampling, use_graph)
+            yield from self._inference_host(sess, rows, min_len, max_len, sampling, use_graph, slots)
             return
         sess.start([rows], [min_len], [max_len], [self._request_seed() if seed is None else seed], cfg,
-                   uniforms=uniforms)
+                   uniforms=uniforms, slots=slots)
         while True:
             tok, done, err = sess.read()
             if err[0]:
@@ -246,9 +255,18 @@ class TransformerLM(nn.Module):
                 return
             sess.advance(use_graph)
 
-    def _inference_host(self, sess, rows, min_len, max_len, sampling, use_graph):
+    def _adapter_slots(self, adapters, activate: bool = True):
+        """(the model's AdapterBank, each request's decode slot); with one request its adapter is also activated."""
+        from .adapters import bank_of
+        bank = bank_of(self)
+        slots = [bank.slot(a) for a in adapters]
+        if activate and len(adapters) == 1:
+            bank.activate(adapters[0])
+        return bank, slots
+
+    def _inference_host(self, sess, rows, min_len, max_len, sampling, use_graph, slots=None):
         """an arbitrary ``self.sampling`` callable: device logits / log_softmax, the draw on the host per step."""
-        sess.start([rows], [0], [max_len], [0], DEC.SamplerCfg("logp"))
+        sess.start([rows], [0], [max_len], [0], DEC.SamplerCfg("logp"), slots=slots)
         out: List[int] = []
         for i in range(max_len):
             logp = sess.logp[0].clone()
@@ -270,12 +288,19 @@ class TransformerLM(nn.Module):
                         prompt_texts: Optional[Sequence[torch.Tensor]] = None,
                         prompt_speech_tokens: Optional[Sequence[torch.Tensor]] = None,
                         seeds: Optional[Sequence[int]] = None, max_token_text_ratio: float = 20,
-                        min_token_text_ratio: float = 2, use_graph: bool = True) -> List[List[int]]:
+                        min_token_text_ratio: float = 2, use_graph: bool = True,
+                        adapters: Optional[Sequence] = None) -> List[List[int]]:
         """Up to 16 requests (ragged) decoded in lockstep: each is prefilled into its own cache row, then every step
         streams the weights once for all rows; finished rows are skipped by the kernels.  Returns one token list per
-        request, equal to what ``inference`` yields for that request with the same seed."""
+        request, equal to what ``inference`` yields for that request with the same seed.  adapters: one name (or
+        adapters.BASE) per request, as ``inference(adapter=)``: the base weights are streamed once and every row adds its
+        own adapter; None decodes the module's own (merged) weights."""
         B = len(texts)
         assert 1 <= B <= 16, "inference_batch: 1 .. 16 requests"
+        bank, slots = (None, None)
+        if adapters is not None:
+            assert len(adapters) == B, "inference_batch: one adapter per request"
+            bank, slots = self._adapter_slots(list(adapters), activate=False)
         cfg = self.sampler_cfg()
         if cfg is None:
             raise NotImplementedError("inference_batch runs the device sampler only (see sampler_cfg)")
@@ -285,6 +310,8 @@ class TransformerLM(nn.Module):
             pt = prompt_texts[b] if prompt_texts is not None else z
             ps = prompt_speech_tokens[b] if prompt_speech_tokens is not None else z
             emb = embeddings[b] if embeddings is not None else torch.zeros(1, 192)
+            if bank is not None:
+                bank.activate(adapters[b])             # the text encoder runs through its modules: this request's adapter
             r, n = self.lm_input_rows(texts[b].reshape(-1), texts[b].numel(), pt.reshape(-1), pt.numel(),
                                       ps.reshape(-1), ps.numel(), emb.reshape(1, -1) if emb.numel() else emb)
             rows.append(r)
@@ -294,8 +321,8 @@ class TransformerLM(nn.Module):
         outs: List[List[int]] = [[] for _ in range(B)]
         if max(maxs) <= 0:
             return outs
-        sess = self.decode_session(B, max(r.shape[0] + m for r, m in zip(rows, maxs)))
-        sess.start(rows, mins, [max(m, 1) for m in maxs], seeds, cfg)
+        sess = self.decode_session(B, max(r.shape[0] + m for r, m in zip(rows, maxs)), bank=bank)
+        sess.start(rows, mins, [max(m, 1) for m in maxs], seeds, cfg, slots=slots)
         active = [m > 0 for m in maxs]
         while any(active):
             tok, done, err = sess.read()

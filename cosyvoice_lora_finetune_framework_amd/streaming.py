@@ -187,7 +187,7 @@ class StreamingSynthesizer:
             prompt_feat: Optional[torch.Tensor] = None, stream: bool = True, speed: float = 1.0, seed: Optional[int] = None,
             source_speech_token: Optional[Sequence[int]] = None, noise=None, hift_seed: Optional[int] = None,
             hift_draws=None, hift_dtype=None, use_graph: bool = True, want_pcm: bool = False,
-            llm_kw: Optional[dict] = None) -> Iterator[dict]:
+            llm_kw: Optional[dict] = None, adapter=None) -> Iterator[dict]:
         """Generator of {'tts_speech': [1, n] fp32 on the device, complete when it is yielded} (with want_pcm also
         'pcm': [n] int16).  stream=False yields one item: the whole utterance through one final token2wav, as the reference's
         tts(stream=False) does.  With an empty prompt that is inference_joint.synthesize + vocode bit for bit (at any
@@ -195,9 +195,14 @@ class StreamingSynthesizer:
         source_speech_token skips the LLM (the reference's vc_job).  seed pins the LLM's sampler; noise (one tensor, or one
         per chunk) the Flow's initial z; hift_seed the vocoder's draws (chunk i draws with hift_seed + i) and hift_draws
         (one pair per chunk) replaces them.  prompt_feat [1, frames, 80] (log-mel, not normalised) may be given in place
-        of prompt_wav; llm_kw: further keywords of ``llm.inference`` (the token / text ratios).  After the generator ends,
+        of prompt_wav; llm_kw: further keywords of ``llm.inference`` (the token / text ratios).  adapter: a voice resident in the
+        models' adapters.AdapterBank (or adapters.BASE), as ``inference_joint.synthesize(adapter=)``; it is written into the
+        modules on the caller's stream before the LLM's stream forks off.  After the generator ends,
         ``last_timing`` holds the host's view of the overlap."""
         dev = self.flow.input_embedding.weight.device
+        if adapter is not None:
+            from .inference_joint import activate_adapter
+            activate_adapter(self.llm, self.flow, adapter)
         p_tok, p_text, emb, p_feat = self._prompt(dev, prompt_wav, prompt_rate, prompt_speech_token, prompt_text, embedding)
         if prompt_feat is not None:
             p_feat = prompt_feat.float().to(dev)
@@ -225,7 +230,8 @@ class StreamingSynthesizer:
             text = torch.as_tensor(text_tokens, dtype=torch.long).reshape(1, -1).to(dev)
             n = lambda t: torch.tensor([t.shape[1]])                                                    # noqa: E731
             tokens_it = self.llm.inference(text, n(text), p_text, n(p_text), p_tok, n(p_tok), emb, seed=seed,
-                                           use_graph=use_graph, **(llm_kw or {}))
+                                           use_graph=use_graph, **({} if adapter is None else {'adapter': adapter}),
+                                           **(llm_kw or {}))
             llm_stream = self.llm_stream(dev) if stream else None
 
         if not stream:

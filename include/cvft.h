@@ -578,6 +578,22 @@ int cvft_debug_mfma_fp8_probe(const void* A, const void* B, float* C, void* stre
 int cvft_decode_linear(int wdtype, int M, int N, int K, const float* X, int ldx, const float* ln_g, const float* ln_b,
                        float ln_eps, const void* W, const float* bias, int act, const float* residual, int ldr, float* Y,
                        int ldy, void* stream);
+/* Per-row LoRA adapters on the decode linears (adapters.py AdapterBank; weights stay unfolded).  The adapters of S slots
+ * are stacked in the weights' dtype: A [S][G][R][K], Bst [S][N][R], scale [S] fp32 (alpha / r of the slot's adapter; ranks
+ * below R are zero-padded).  slot [M] (device int32) names each row's adapter; a slot < 0 or >= S is "no adapter".
+ * cvft_decode_lora_down: Z[m][g*R + j] = LN?(X)[m,:] . A[slot[m]][g][j][:] (zeros for a row without adapter, the stack is
+ *   not read).  G = 1, or 3 for the stacked q | k | v adapters of one input; R in {8, 16, 32, 64}; K % 8 == 0; ldz >= G*R.
+ *   One workgroup per (8 values of j, g, m): a row's result depends on that row alone.
+ * cvft_decode_linear_lora: cvft_decode_linear (same main loop) whose epilogue adds, before the activation and the residual,
+ *   scale[s] * sum_j Bst[s][n][j] * Z[m][(n / (N/G))*R + j] with s = slot[m]; a row without adapter gets exactly
+ *   cvft_decode_linear's result.  N % G == 0, ldz % 4 == 0. */
+int cvft_decode_lora_down(int wdtype, int M, int K, int S, int G, int R, const float* X, int ldx, const float* ln_g,
+                          const float* ln_b, float ln_eps, const void* A, const int32_t* slot, float* Z, int ldz,
+                          void* stream);
+int cvft_decode_linear_lora(int wdtype, int M, int N, int K, const float* X, int ldx, const float* ln_g, const float* ln_b,
+                            float ln_eps, const void* W, const float* bias, int act, const float* residual, int ldr,
+                            float* Y, int ldy, int S, int G, int R, const void* Bst, const float* scale,
+                            const int32_t* slot, const float* Z, int ldz, void* stream);
 int cvft_decode_attn(int B, int H, int Lq, int cap, int nsplit, const float* qkv, int ldqkv, float* kc, float* vc,
                      const int32_t* len, const int32_t* done, const float* P, int ldp, const float* pos_bias_u,
                      const float* pos_bias_v, float scale, float* part, float* o, int ldo, void* stream);
