@@ -288,25 +288,28 @@ int launch_linear_lora(int M, int N, int K, const float* X, int ldx, const float
 }
 
 // ---------------------------------------------------------------- decode attention
-__global__ __launch_bounds__(ATT_KEYS) void decode_attn_split_kernel(
-    int H, int Lq, int cap, int nsplit, const float* __restrict__ qkv, int ldqkv, float* kc, float* vc,
-    const int32_t* __restrict__ len, const int32_t* __restrict__ done, const float* __restrict__ P, int ldp,
+// One (key split s, head h) workgroup of the Lq new rows q0 .. q0+Lq-1 of `qkv` against cache row b: the body of both the
+// uniform (B, Lq) launch (q0 = b * Lq) and the ragged one (a segment table).  Its slice of `part` is indexed per
+// (query row, head, split): the Lq*H*nsplit*66 floats from q0*H*nsplit*66, laid out [h][s][r][66].
+__device__ __forceinline__ void decode_attn_split_body(
+    int b, int q0, int Lq, bool skip, int s, int h, int H, int cap, int nsplit, const float* __restrict__ qkv, int ldqkv,
+    float* kc, float* vc, const int32_t* __restrict__ len, const float* __restrict__ P, int ldp,
     const float* __restrict__ pbu, const float* __restrict__ pbv, float scale, float* __restrict__ part) {
     __shared__ float s_qu[MAX_LQ][64], s_qv[MAX_LQ][64];
     __shared__ float s_p[MAX_LQ][ATT_KEYS];
-    const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z, t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
+    const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
     const int D = H * 64;
-    float* pr = part + ((size_t)(b * H + h) * nsplit + s) * Lq * 66;
+    float* pr = part + (((size_t)q0 * H + (size_t)h * Lq) * nsplit + (size_t)s * Lq) * 66;
     const int L0 = len[b];
     const int n = min(L0 + Lq, cap);
     const int j0 = s * ATT_KEYS;
-    if ((done && done[b]) || j0 >= n) {
+    if (skip || j0 >= n) {
         for (int r = t; r < Lq; r += ATT_KEYS) { pr[r * 66 + 64] = -INFINITY; pr[r * 66 + 65] = 0.f; }
         return;
     }
     for (int i = t; i < Lq * 64; i += ATT_KEYS) {
         const int r = i / 64, d = i % 64;
-        const float q = qkv[(size_t)(b * Lq + r) * ldqkv + h * 64 + d];
+        const float q = qkv[(size_t)(q0 + r) * ldqkv + h * 64 + d];
         s_qu[r][d] = q + pbu[h * 64 + d];
         s_qv[r][d] = q + pbv[h * 64 + d];
     }
@@ -314,7 +317,7 @@ __global__ __launch_bounds__(ATT_KEYS) void decode_attn_split_kernel(
     const int j = j0 + t;
     const size_t crow = ((size_t)(b * H + h) * cap + j) * 64;
     if (j < n) {
-        const float* kp = j < L0 ? kc + crow : qkv + (size_t)(b * Lq + (j - L0)) * ldqkv + D + h * 64;
+        const float* kp = j < L0 ? kc + crow : qkv + (size_t)(q0 + (j - L0)) * ldqkv + D + h * 64;
         f32x4 k[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) k[i] = reinterpret_cast<const f32x4*>(kp)[i];
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(ATT_KEYS) void decode_attn_split_kernel(
             s_p[r][t] = sc;
         }
         if (j >= L0) {        // append the new row's K/V (nobody reads cache rows >= len[b] in this launch)
-            const float* vp = qkv + (size_t)(b * Lq + (j - L0)) * ldqkv + 2 * D + h * 64;
+            const float* vp = qkv + (size_t)(q0 + (j - L0)) * ldqkv + 2 * D + h * 64;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 reinterpret_cast<f32x4*>(kc + crow)[i] = k[i];
@@ -370,22 +373,22 @@ __global__ __launch_bounds__(ATT_KEYS) void decode_attn_split_kernel(
         for (int jj = 0; jj < cnt; ++jj) {
             const int jk = j0 + jj;
             const float vv = jk < L0 ? vc[((size_t)(b * H + h) * cap + jk) * 64 + d]
-                                     : qkv[(size_t)(b * Lq + (jk - L0)) * ldqkv + 2 * D + h * 64 + d];
+                                     : qkv[(size_t)(q0 + (jk - L0)) * ldqkv + 2 * D + h * 64 + d];
             o = fmaf(s_p[r][jj], vv, o);
         }
         pr[r * 66 + d] = o;
     }
 }
 
-__global__ __launch_bounds__(64) void decode_attn_combine_kernel(int H, int Lq, int nsplit, const int32_t* __restrict__ done,
-                                                                 const float* __restrict__ part, float* __restrict__ o,
-                                                                 int ldo) {
-    const int r = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-    const float* pr = part + (size_t)(b * H + h) * nsplit * Lq * 66 + r * 66;
+// The two-stage max / sum combine of query row q0 + r, head h over the splits (one thread per channel).
+__device__ __forceinline__ void decode_attn_combine_body(int q0, int Lq, int r, bool skip, int h, int H, int nsplit,
+                                                         const float* __restrict__ part, float* __restrict__ o, int ldo) {
+    const int d = threadIdx.x;
+    const float* pr = part + ((size_t)q0 * H + (size_t)h * Lq) * nsplit * 66 + r * 66;
     float mx = -INFINITY;
     for (int s = 0; s < nsplit; ++s) mx = fmaxf(mx, pr[(size_t)s * Lq * 66 + 64]);
     float l = 0.f, acc = 0.f;
-    if (mx != -INFINITY && !(done && done[b])) {
+    if (mx != -INFINITY && !skip) {
         for (int s = 0; s < nsplit; ++s) {
             const float* ps = pr + (size_t)s * Lq * 66;
             const float ms = ps[64];
@@ -395,7 +398,51 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(int H, int Lq, 
             acc += ps[d] * w;
         }
     }
-    o[(size_t)(b * Lq + r) * ldo + h * 64 + d] = l > 0.f ? acc / l : 0.f;
+    o[(size_t)(q0 + r) * ldo + h * 64 + d] = l > 0.f ? acc / l : 0.f;
+}
+
+__global__ __launch_bounds__(ATT_KEYS) void decode_attn_split_kernel(
+    int H, int Lq, int cap, int nsplit, const float* __restrict__ qkv, int ldqkv, float* kc, float* vc,
+    const int32_t* __restrict__ len, const int32_t* __restrict__ done, const float* __restrict__ P, int ldp,
+    const float* __restrict__ pbu, const float* __restrict__ pbv, float scale, float* __restrict__ part) {
+    const int b = blockIdx.z;
+    decode_attn_split_body(b, b * Lq, Lq, done && done[b], blockIdx.x, blockIdx.y, H, cap, nsplit, qkv, ldqkv, kc, vc, len, P,
+                           ldp, pbu, pbv, scale, part);
+}
+
+__global__ __launch_bounds__(64) void decode_attn_combine_kernel(int H, int Lq, int nsplit, const int32_t* __restrict__ done,
+                                                                 const float* __restrict__ part, float* __restrict__ o,
+                                                                 int ldo) {
+    const int b = blockIdx.z;
+    decode_attn_combine_body(b * Lq, Lq, blockIdx.x, done && done[b], blockIdx.y, H, nsplit, part, o, ldo);
+}
+
+// Ragged form: sequence z is the segment seg[z] = (cache row b, first activation row q0, Lq).  A segment that does not fit
+// the launch (b outside [0, nrows), rows outside [0, M)) is skipped whole, so a bad table reads and writes nothing.
+__device__ __forceinline__ bool decode_attn_segment(const int32_t* __restrict__ seg, int z, int M, int nrows, int& b, int& q0,
+                                                    int& Lq) {
+    b = seg[3 * z];
+    q0 = seg[3 * z + 1];
+    Lq = seg[3 * z + 2];
+    return b >= 0 && b < nrows && q0 >= 0 && Lq >= 1 && Lq <= MAX_LQ && q0 + Lq <= M;
+}
+
+__global__ __launch_bounds__(ATT_KEYS) void decode_attn_ragged_split_kernel(
+    const int32_t* __restrict__ seg, int M, int nrows, int H, int cap, int nsplit, const float* __restrict__ qkv, int ldqkv,
+    float* kc, float* vc, const int32_t* __restrict__ len, const float* __restrict__ P, int ldp,
+    const float* __restrict__ pbu, const float* __restrict__ pbv, float scale, float* __restrict__ part) {
+    int b, q0, Lq;
+    if (!decode_attn_segment(seg, blockIdx.z, M, nrows, b, q0, Lq)) return;
+    decode_attn_split_body(b, q0, Lq, false, blockIdx.x, blockIdx.y, H, cap, nsplit, qkv, ldqkv, kc, vc, len, P, ldp, pbu,
+                           pbv, scale, part);
+}
+
+__global__ __launch_bounds__(64) void decode_attn_ragged_combine_kernel(
+    const int32_t* __restrict__ seg, int M, int nrows, int H, int nsplit, const float* __restrict__ part,
+    float* __restrict__ o, int ldo) {
+    int b, q0, Lq;
+    if (!decode_attn_segment(seg, blockIdx.z, M, nrows, b, q0, Lq) || (int)blockIdx.x >= Lq) return;
+    decode_attn_combine_body(q0, Lq, blockIdx.x, false, blockIdx.y, H, nsplit, part, o, ldo);
 }
 
 // ---------------------------------------------------------------- sampler
@@ -680,6 +727,27 @@ extern "C" int cvft_decode_attn(int B, int H, int Lq, int cap, int nsplit, const
                        kc, vc, len, done, P, ldp, pos_bias_u, pos_bias_v, scale, part);
     hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(Lq, H, B), dim3(64), 0, s, H, Lq, nsplit, done, part, o, ldo);
     CVFT_LAUNCH_CHECK("cvft_decode_attn");
+    return 0;
+}
+
+extern "C" int cvft_decode_attn_ragged(int nseg, int M, int nrows, int H, int cap, int nsplit, const int32_t* seg,
+                                       const float* qkv, int ldqkv, float* kc, float* vc, const int32_t* len,
+                                       const float* P, int ldp, const float* pos_bias_u, const float* pos_bias_v,
+                                       float scale, float* part, float* o, int ldo, void* stream) {
+    CVFT_CHECK_ARG(nseg >= 1 && nseg <= MAX_LQ && M >= nseg && M <= MAX_LQ && nrows >= 1 && H >= 1,
+                   "cvft_decode_attn_ragged: nseg=%d M=%d nrows=%d H=%d (1 <= nseg <= M <= 16)", nseg, M, nrows, H);
+    CVFT_CHECK_ARG(cap >= 1 && nsplit >= 1 && (long)nsplit * ATT_KEYS >= cap,
+                   "cvft_decode_attn_ragged: nsplit*256 < cap (%d, %d)", nsplit, cap);
+    CVFT_CHECK_ARG(seg && qkv && kc && vc && len && P && pos_bias_u && pos_bias_v && part && o,
+                   "cvft_decode_attn_ragged: null pointer");
+    CVFT_CHECK_ARG(ldqkv >= 3 * H * 64 && ldqkv % 4 == 0 && ldp >= H * 64 && ldp % 4 == 0 && ldo >= H * 64,
+                   "cvft_decode_attn_ragged: bad strides");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(decode_attn_ragged_split_kernel, dim3(nsplit, H, nseg), dim3(ATT_KEYS), 0, s, seg, M, nrows, H, cap,
+                       nsplit, qkv, ldqkv, kc, vc, len, P, ldp, pos_bias_u, pos_bias_v, scale, part);
+    hipLaunchKernelGGL(decode_attn_ragged_combine_kernel, dim3(MAX_LQ, H, nseg), dim3(64), 0, s, seg, M, nrows, H, nsplit,
+                       part, o, ldo);
+    CVFT_LAUNCH_CHECK("cvft_decode_attn_ragged");
     return 0;
 }
 

@@ -11,6 +11,12 @@ once as a hipGraph per (batch, capacity) on one stream; the host reads tokens + 
 Prefill runs through the same kernels in chunks of <= 16 rows (the causal attention of a chunk against the cache is
 exactly the reference's full causal prefill).  The text encoder still runs through the training forward
 (``RelPosEncoder.forward_cl``), like ``TransformerLM.encode`` with decoding_chunk_size=1.
+
+Continuous batching: ``LMDecodeSession.admit`` / ``serve_step`` / ``retire`` let a request join a
+running batch in a free cache row and leave it when it ends, without touching the captured step (it reads only device state
+at fixed addresses).  A newcomer's prompt is prefilled either between two decode steps or a few rows per step alongside the
+decode rows: one pass over the linears, and the ragged attention (``decode_attn_ragged``: a segment table instead of a
+uniform (B, Lq)).  ``RowScheduler`` is the host-only schedule; ``llm_model.DecodeServer`` is the public front.
 """
 from __future__ import annotations
 
@@ -102,6 +108,30 @@ def decode_attn(qkv, kc, vc, length, P, pos_bias_u, pos_bias_v, B: int, H: int, 
     check(lib().cvft_decode_attn(B, H, Lq, cap, nsplit, ptr(qkv), qkv.stride(0), ptr(kc), ptr(vc), ptr(length), ptr(done),
                                  ptr(P), P.stride(0), ptr(pos_bias_u), ptr(pos_bias_v), 1.0 / math.sqrt(64.0), ptr(part),
                                  ptr(out), out.stride(0), stream()), "cvft_decode_attn")
+    return out
+
+
+def decode_attn_ragged(qkv, kc, vc, length, P, pos_bias_u, pos_bias_v, seg, nseg: int, H: int, part=None,
+                       out=None) -> torch.Tensor:
+    """decode_attn driven by a segment table: seg [>= nseg, 3] int32 (device) = (cache row b, first activation row q0, Lq),
+    nseg <= 16 live sequences whose rows are disjoint and sum to <= 16.  qkv [M <= 16, >= 3*H*64], kc / vc
+    [rows, H, cap, 64] (all cache rows; only the named ones are read and appended to, at length[b]), length [rows] int32
+    -> o [M, H*64] (rows no segment names are left as they are).  Every row equals decode_attn of its sequence alone."""
+    M = qkv.shape[0]
+    nrows, cap = kc.shape[0], kc.shape[2]
+    nsplit = -(-cap // ATT_KEYS)
+    D = H * 64
+    if part is None:
+        part = torch.empty(M * H * nsplit * 66, dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = torch.zeros((M, D), dtype=torch.float32, device=qkv.device)
+    assert 1 <= nseg <= M <= MAX_ROWS and out.shape[0] >= M and part.numel() >= M * H * nsplit * 66
+    assert seg.dtype == torch.int32 and seg.is_contiguous() and seg.numel() >= 3 * nseg
+    assert P.shape[0] >= cap and kc.is_contiguous() and vc.is_contiguous() and vc.shape == kc.shape and length.numel() >= nrows
+    check(lib().cvft_decode_attn_ragged(nseg, M, nrows, H, cap, nsplit, ptr(seg), ptr(qkv), qkv.stride(0), ptr(kc), ptr(vc),
+                                        ptr(length), ptr(P), P.stride(0), ptr(pos_bias_u), ptr(pos_bias_v),
+                                        1.0 / math.sqrt(64.0), ptr(part), ptr(out), out.stride(0), stream()),
+          "cvft_decode_attn_ragged")
     return out
 
 
@@ -222,34 +252,43 @@ class DecodeStack:
         g, b, eps = self.ln_emb
         return _layernorm(self.e[:M], g, b, eps, self.h[:M], self.mean, self.rstd, self.emb_relu, self.emb_scale)
 
-    def layers_fwd(self, B: int, Lq: int, row: Optional[int] = None, lora=None):
+    def layers_fwd(self, B: int, Lq: int, row: Optional[int] = None, lora=None, seg=None):
         """the layers over self.h[:B*Lq] (Lq new rows per sequence).  row: a single cache row (prefill of one request).
         lora = (an AdapterBank's per-layer stacks, slot [>= B*Lq] int32): every linear becomes down -> linear_lora with
-        each row's own adapter (the pack is then the unfolded one)."""
-        M = B * Lq
+        each row's own adapter (the pack is then the unfolded one).  seg = (table [>= nseg, 3] int32 on the device, nseg,
+        M): the M rows of self.h are the sequences of that segment table (decode_attn_ragged); B, Lq and row are unused."""
+        if seg is None:
+            M = B * Lq
+            sl = slice(None) if row is None else slice(row, row + 1)
+            length = self.len[sl]
+            done = self.done[sl]
+
+            def attn(i, L, qkv):
+                return decode_attn(qkv, self.kc[i, sl], self.vc[i, sl], length, self.P[i], L["u"], L["v"], B, self.H, Lq,
+                                   done=done, part=self.part, out=self.o[:M])
+        else:
+            table, nseg, M = seg
+
+            def attn(i, L, qkv):
+                return decode_attn_ragged(qkv, self.kc[i], self.vc[i], self.len, self.P[i], L["u"], L["v"], table, nseg,
+                                          self.H, part=self.part, out=self.o[:M])
         h = self.h[:M]
-        sl = slice(None) if row is None else slice(row, row + 1)
-        length = self.len[sl]
-        done = self.done[sl]
         if lora is not None:
-            return self._layers_fwd_lora(B, Lq, h, sl, length, done, *lora)
+            return self._layers_fwd_lora(M, h, attn, *lora)
         for i, L in enumerate(self.layers):
             qkv = decode_linear(h, L["Wqkv"], L["bqkv"], ln=L["ln1"], out=self.qkv[:M])
-            o = decode_attn(qkv, self.kc[i, sl], self.vc[i, sl], length, self.P[i], L["u"], L["v"], B, self.H, Lq, done=done,
-                            part=self.part, out=self.o[:M])
+            o = attn(i, L, qkv)
             decode_linear(o, L["Wo"], L["bo"], residual=h, out=h)
             f = decode_linear(h, L["W1"], L["b1"], ln=L["ln2"], act=1, out=self.f[:M])
             decode_linear(f, L["W2"], L["b2"], residual=h, out=h)
         return h
 
-    def _layers_fwd_lora(self, B, Lq, h, sl, length, done, bank, slot):
-        M = B * Lq
+    def _layers_fwd_lora(self, M, h, attn, bank, slot):
         z, sc = self.z, bank.scale
         for i, (L, A) in enumerate(zip(self.layers, bank.layers)):
             decode_lora_down(h, A["A_qkv"], slot, ln=L["ln1"], out=z[:M])
             qkv = decode_linear_lora(h, L["Wqkv"], A["B_qkv"], sc, slot, z, 3, L["bqkv"], ln=L["ln1"], out=self.qkv[:M])
-            o = decode_attn(qkv, self.kc[i, sl], self.vc[i, sl], length, self.P[i], L["u"], L["v"], B, self.H, Lq, done=done,
-                            part=self.part, out=self.o[:M])
+            o = attn(i, L, qkv)
             decode_lora_down(o, A["A_o"], slot, out=z[:M])
             decode_linear_lora(o, L["Wo"], A["B_o"], sc, slot, z, 1, L["bo"], residual=h, out=h)
             decode_lora_down(h, A["A_1"], slot, ln=L["ln2"], out=z[:M])
@@ -310,6 +349,105 @@ def forward_chunk(enc, xs, offset: int, required_cache_size: int, att_cache=None
     return y.unsqueeze(0).to(xs.dtype), new.to(xs.dtype), torch.zeros((nl, 0, 0, 0), dtype=xs.dtype, device=dev)
 
 
+# ---------------------------------------------------------------------------------------------- serving: the schedule
+def check_serve_rows(rows: int, prefill_rows: int) -> None:
+    if rows < 1 or prefill_rows < 0 or rows + prefill_rows > MAX_ROWS:
+        raise ValueError(f"rows {rows} + prefill_rows {prefill_rows}: at least one row, and at most {MAX_ROWS} activation "
+                         f"rows per decode launch")
+
+
+def prefill_chunks(T: int, prefill_rows: int) -> List[int]:
+    """the chunk sizes a prompt of T rows is prefilled in: <= prefill_rows per mixed step, or (prefill_rows = 0, stall)
+    the <= 16-row chunks of the prefill path, which all run in one step."""
+    n = prefill_rows if prefill_rows > 0 else MAX_ROWS
+    return [min(n, T - c0) for c0 in range(0, T, n)]
+
+
+class RowScheduler:
+    """The host-only part of continuous batching: which queued request takes which cache row, and which prompt rows run
+    in which step.  Requests are admitted one at a time in FIFO order into the lowest free row; a request's first token
+    is due in the step that consumes the last row of its prompt."""
+
+    def __init__(self, rows: int, prefill_rows: int):
+        check_serve_rows(rows, prefill_rows)
+        self.rows, self.prefill_rows = rows, prefill_rows
+        self.free = list(range(rows))
+        self.queue: List[tuple] = []                       # (rid, prompt rows), oldest first
+        self.row_of: dict = {}                             # rid -> row (admitted, not released)
+        self.flight: Optional[list] = None                 # [rid, row, chunk sizes still to run]
+
+    def submit(self, rid, T: int) -> None:
+        self.queue.append((rid, int(T)))
+
+    def release(self, rid) -> Optional[int]:
+        """the request leaves (finished or cancelled, at any stage); -> the row it held, free again, or None if it was
+        still queued."""
+        for i, (q, _) in enumerate(self.queue):
+            if q == rid:
+                del self.queue[i]
+                return None
+        row = self.row_of.pop(rid)
+        if self.flight is not None and self.flight[0] == rid:
+            self.flight = None
+        self.free.append(row)
+        self.free.sort()
+        return row
+
+    def busy(self) -> bool:
+        return bool(self.queue or self.row_of)
+
+    def plan(self) -> dict:
+        """the next step: {'admit': (rid, row) | None -- the request to admit before it, 'rid' / 'row' / 'chunks': the
+        prompt chunks this step runs for the admission in flight ([] when there is none), 'first': whether that request's
+        first token is due in this step's read}."""
+        admit = None
+        if self.flight is None and self.queue and self.free:
+            rid, T = self.queue.pop(0)
+            row = self.free.pop(0)
+            self.row_of[rid] = row
+            self.flight = [rid, row, prefill_chunks(T, self.prefill_rows)]
+            admit = (rid, row)
+        if self.flight is None:
+            return dict(admit=None, rid=None, row=None, chunks=[], first=False)
+        rid, row, left = self.flight
+        chunks = left[:] if self.prefill_rows == 0 else left[:1]
+        del left[:len(chunks)]
+        if not left:
+            self.flight = None
+        return dict(admit=admit, rid=rid, row=row, chunks=chunks, first=not left)
+
+
+def serve_schedule(rows: int, prefill_rows: int, requests: Sequence[tuple]) -> List[dict]:
+    """The schedule of requests = [(arrival step, prompt rows, tokens it will decode), ...] (in arrival order) on the
+    RowScheduler, without a device: per request {'row', 'admit_step', 'chunks': [(step, size), ...], 'first_step': the
+    step whose read carries its first token, 'last_step': the step of its last token}."""
+    sch = RowScheduler(rows, prefill_rows)
+    out = [dict(row=None, admit_step=None, chunks=[], first_step=None, last_step=None) for _ in requests]
+    left = {}
+    step, nxt = 0, 0
+    while nxt < len(requests) or sch.busy():
+        while nxt < len(requests) and requests[nxt][0] <= step:
+            sch.submit(nxt, requests[nxt][1])
+            nxt += 1
+        p = sch.plan()
+        if p["admit"] is not None:
+            rid, row = p["admit"]
+            out[rid].update(row=row, admit_step=step)
+        for rid in list(left):                               # every decoding row draws one token
+            left[rid] -= 1
+        if p["rid"] is not None:
+            out[p["rid"]]["chunks"] += [(step, n) for n in p["chunks"]]
+            if p["first"]:
+                out[p["rid"]]["first_step"] = step
+                left[p["rid"]] = requests[p["rid"]][2] - 1
+        for rid in [r for r, n in left.items() if n <= 0]:
+            out[rid]["last_step"] = step
+            del left[rid]
+            sch.release(rid)
+        step += 1
+    return out
+
+
 class SamplerCfg:
     def __init__(self, mode: str, top_p: float = 0.8, top_k: int = 25, win_size: int = 10, tau_r: float = 0.1):
         self.mode, self.top_p, self.top_k, self.win = mode, float(top_p), int(top_k), int(win_size)
@@ -336,10 +474,18 @@ class PackedLM:
 class LMDecodeSession:
     """B rows of lockstep decode of a TransformerLM (see the module docstring) over shared packed weights."""
 
-    def __init__(self, packed: PackedLM, B: int, cap: int, bank=None):
+    def __init__(self, packed: PackedLM, B: int, cap: int, bank=None, prefill_rows: int = 0):
         """bank: an adapters.AdapterBank's stacks for packed.wdtype (the pack is then the unfolded one): every row decodes
-        with the adapter whose slot stands in self.slot (-1: none); the captured step holds the stacks' fixed addresses."""
+        with the adapter whose slot stands in self.slot (-1: none); the captured step holds the stacks' fixed addresses.
+        prefill_rows (admit / serve_step only): 0 prefills an admitted request between two decode steps; n > 0 carries up
+        to n of its prompt rows along with every decode step (B + n <= 16)."""
+        check_serve_rows(B, prefill_rows)
+        self.prefill_rows = int(prefill_rows)
+        self.live: set = set()            # rows that decode (admitted, first token drawn, not retired): host view
+        self.adm: Optional[dict] = None   # the admission in flight: row, prompt rows, rows consumed, slot
+        self.slots = [-1] * B
         dev = packed.stack.dev
+        self.seg = torch.zeros((MAX_ROWS, 3), dtype=torch.int32, device=dev)                # the mixed step's segment table
         self.wdtype = packed.wdtype
         assert (bank is None) == packed.folded, "a folded pack decodes without a bank, an unfolded one with one"
         self.bank = bank
@@ -449,3 +595,115 @@ class LMDecodeSession:
         """(tokens, done, err) of the last step as host lists (the one device->host read per step)."""
         s = torch.stack([self.tok, self.stack.done, self.err]).cpu()
         return s[0].tolist(), s[1].tolist(), s[2].tolist()
+
+    # ---- continuous batching: rows join and leave a running batch (llm_model.DecodeServer drives these)
+    def _sample_row(self, b: int):
+        """the sampler for row b alone (B = 1, every per-row pointer at row b); lengths are not bumped."""
+        c, st, V = self.cfg, self.stack, self.V
+        u = None if self.uniforms is None else self.uniforms[b]
+        check(lib().cvft_decode_sample(1, V, ptr(self.logits[b]), V, ptr(self.logp[b]), self.eos, MODES[c.mode], c.top_k,
+                                       c.top_p, c.win, c.rep_thr, ptr(self.seeds[b:]), ptr(u), ptr(self.tok[b:]),
+                                       ptr(self.next_in[b:]), ptr(self.hist[b]), HIST, ptr(self.nhist[b:]),
+                                       ptr(self.step[b:]), ptr(self.min_len[b:]), ptr(self.max_len[b:]), None,
+                                       ptr(st.done[b:]), ptr(self.err[b:]), stream()), "cvft_decode_sample")
+
+    def idle(self, cfg: SamplerCfg):
+        """every row free (done, so the captured step skips it), nothing in flight; `cfg` is the sampler of all admissions."""
+        assert cfg.mode != "logp", "admit / serve_step run the device sampler"
+        self.cfg = cfg
+        self.uniforms = None
+        self.stack.done.fill_(1)
+        self.live.clear()
+        self.adm = None
+
+    def admit(self, b: int, x: torch.Tensor, min_len: int, max_len: int, seed: int, slot: Optional[int] = None,
+              uniforms: Optional[torch.Tensor] = None):
+        """Start request x [T, input] (its lm_input rows) in the free cache row b while the other rows keep decoding: row
+        b's state alone is reset (its K/V needs no clearing, nothing reads past len[b]) and it stays `done` until its
+        prompt is in the cache, so the all-rows sampler and the captured step skip it.  The prompt is consumed by the
+        following serve_step calls; the read() after the last of its rows carries the request's first token.  One
+        admission at a time.  uniforms [101, 2]: pinned draws for every step of this request (then every live row must
+        have pinned draws: the sampler takes all of them or none)."""
+        st = self.stack
+        T = int(x.shape[0])
+        if T + int(max_len) > self.cap:
+            raise ValueError("decode capacity bucket too small")
+        if not 0 <= b < self.B or b in self.live or T < 1 or int(max_len) < 1:
+            raise ValueError(f"admit: row {b} of {self.B} (decoding rows {sorted(self.live)}), {T} prompt rows, max_len {max_len}")
+        if self.adm is not None:
+            raise RuntimeError("admit: another admission is in flight")
+        if (slot is not None) != (self.bank is not None):
+            raise ValueError("admit: a slot goes with a bank session")
+        if self.live and (uniforms is None) != (self.uniforms is None):
+            raise ValueError("admit: pinned uniforms for all live rows or for none")
+        if uniforms is not None:
+            self.ubuf[b].copy_(uniforms.reshape(TRIALS, 2))
+        self.uniforms = self.ubuf if uniforms is not None else None
+        st.done[b:b + 1].fill_(1)
+        for t in (st.len, self.tok, self.next_in, self.nhist, self.step, self.err):
+            t[b:b + 1].zero_()
+        self.hist[b].zero_()
+        self.min_len[b:b + 1].fill_(int(min_len))
+        self.max_len[b:b + 1].fill_(int(max_len))
+        self.seeds[b:b + 1].fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        self.slots[b] = -1 if slot is None else int(slot)
+        self.slot[b:b + 1].fill_(self.slots[b])
+        self.adm = dict(row=b, x=x.float().contiguous(), pos=0)
+
+    def retire(self, b: int):
+        """free row b (a finished or cancelled request, or the admission in flight): done, so every later step skips it."""
+        self.stack.done[b:b + 1].fill_(1)
+        self.live.discard(b)
+        if self.adm is not None and self.adm["row"] == b:
+            self.adm = None
+
+    def serve_step(self, prefill: int = 0, use_graph: bool = True):
+        """One step of the running batch: every decoding row draws its next token, and `prefill` more prompt rows of the
+        admission in flight enter its cache row (the scheduler's chunk: with prefill_rows = 0 the whole prompt, else at
+        most prefill_rows).  Without prefill work this is advance(): the captured step, which reads nothing but device
+        state at fixed addresses, so rows that joined or left since its capture change nothing about it."""
+        a = self.adm
+        if a is None or prefill == 0:
+            assert prefill == 0, "serve_step: no admission in flight"
+            if self.live:
+                self.advance(use_graph)
+            return
+        b, x, pos = a["row"], a["x"], a["pos"]
+        T = x.shape[0]
+        last = pos + prefill == T
+        if self.prefill_rows == 0:
+            # stall: the decode step of the others first (row b is still done), then b's prompt through the prefill path
+            assert pos == 0 and last, "serve_step: the stall mode prefills a prompt whole"
+            if self.live:
+                self.advance(use_graph)
+            self.stack.done[b:b + 1].zero_()
+            self._prefill_row(x, b)
+        else:
+            assert 1 <= prefill <= self.prefill_rows and pos + prefill <= T
+            self._mixed_step(b, x[pos:pos + prefill], pos, last)
+        a["pos"] = pos + prefill
+        if last:
+            self._sample_row(b)
+            self.live.add(b)
+            self.adm = None
+
+    def _mixed_step(self, b: int, xc: torch.Tensor, pos: int, last: bool):
+        """a decode step of rows 0 .. B-1 that carries the prompt chunk xc of row b as activation rows B .. B+n-1 through
+        the same weight stream (run eagerly: the segment table and M change from step to step)."""
+        st, B, n = self.stack, self.B, xc.shape[0]
+        M = B + n
+        check(lib().cvft_gather_rows(F32, B, self.table.shape[1], ptr(self.next_in), ptr(self.table), 0.0, ptr(self.xin),
+                                     stream()), "cvft_gather_rows")
+        self.xin[B:M].copy_(xc)
+        self.slot[B:M].fill_(self.slots[b])
+        segs = [(r, r, 1) for r in sorted(self.live)] + [(b, B, n)]
+        self.seg[:len(segs)].copy_(torch.tensor(segs, dtype=torch.int32))
+        st.embed(self.xin[:M], M)
+        h = st.layers_fwd(0, 0, lora=None if self.bank is None else (self.bank, self.slot), seg=(self.seg, len(segs), M))
+        if self.live:
+            decode_linear(h[:B], self.W_dec, self.b_dec, ln=st.after, out=self.logits)
+            self._sample(bump_len=True)
+        st.len[b:b + 1].fill_(pos + n)
+        if last:
+            self._decoder_logits(h, [M - 1], [b])
+            st.done[b:b + 1].zero_()

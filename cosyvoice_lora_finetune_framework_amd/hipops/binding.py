@@ -194,6 +194,7 @@ SIGNATURES = {
     "cvft_decode_linear_lora": [_i, _i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p,
                                 _i, _p],
     "cvft_decode_attn": [_i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _f, _p, _p, _i, _p],
+    "cvft_decode_attn_ragged": [_i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _f, _p, _p, _i, _p],
     "cvft_decode_sample": [_i, _i, _p, _i, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
                            _p],
     "cvft_hift_conv": [C.POINTER(HiftConvArgs), _p],

@@ -194,17 +194,11 @@ class TransformerLM(nn.Module):
         stacks -- loading, evicting or activating adapters leaves both, and their captured steps, as they are."""
         cap = DEC.bucket(cap)
         fold = bank is None
-        ver = tuple(p._version for n, p in self.named_parameters() if fold or 'lora_' not in n)
         dtype = self.numerics.dtype
-        packs = self.__dict__.setdefault("_cvft_decode_weights", {})
         sessions = self.__dict__.setdefault("_cvft_sessions", collections.OrderedDict())
-        pkey = dtype if fold else (dtype, "unfolded")
         tag = None if fold else id(bank)
-        pk = packs.get(pkey)
-        if pk is None or pk[0] != ver:
-            for k in [k for k in sessions if k[2] == dtype and (len(k) == 3) == fold]:
-                del sessions[k]
-            packs[pkey] = pk = (ver, DEC.PackedLM(self, fold=fold))
+        pk = self._decode_pack(fold)
+        ver = pk[0]
         key = (B, cap, dtype) if fold else (B, cap, dtype, tag)
         hit = sessions.get(key)
         if hit is None:
@@ -214,6 +208,33 @@ class TransformerLM(nn.Module):
                 sessions.popitem(last=False)
         sessions.move_to_end(key)
         return hit[1]
+
+    def _decode_version(self, fold: bool):
+        return tuple(p._version for n, p in self.named_parameters() if fold or 'lora_' not in n)
+
+    def _decode_pack(self, fold: bool):
+        """(parameter versions, the PackedLM) of the current weight dtype, shared by every session and server; repacked
+        (and the LRU sessions over the old pack dropped) when a parameter it depends on has changed."""
+        ver = self._decode_version(fold)
+        dtype = self.numerics.dtype
+        packs = self.__dict__.setdefault("_cvft_decode_weights", {})
+        sessions = self.__dict__.setdefault("_cvft_sessions", collections.OrderedDict())
+        pkey = dtype if fold else (dtype, "unfolded")
+        pk = packs.get(pkey)
+        if pk is None or pk[0] != ver:
+            for k in [k for k in sessions if k[2] == dtype and (len(k) == 3) == fold]:
+                del sessions[k]
+            packs[pkey] = pk = (ver, DEC.PackedLM(self, fold=fold))
+        return pk
+
+    def decode_server(self, rows: int = 8, max_cache: int = 1024, prefill_rows: Optional[int] = None,
+                      adapters: bool = False) -> "DecodeServer":
+        """Continuous batching: a DecodeServer that decodes up to `rows` requests at once and admits queued ones into
+        rows as they fall free (see DecodeServer).  max_cache: prompt rows + max_len every request must fit in.
+        prefill_rows: None takes DEFAULT_PREFILL_ROWS; 0 prefills an admitted request between two decode steps, n > 0
+        carries n of its prompt rows along with each decode step (rows + n <= 16).  adapters=True decodes the base
+        weights with each request's adapter of the model's AdapterBank."""
+        return DecodeServer(self, rows, max_cache, DEFAULT_PREFILL_ROWS if prefill_rows is None else prefill_rows, adapters)
 
     def _request_seed(self) -> int:
         # one draw of torch's default generator per request (torch.manual_seed makes a run reproducible)
@@ -337,6 +358,175 @@ class TransformerLM(nn.Module):
             if any(active):
                 sess.advance(use_graph)
         return outs
+
+
+DEFAULT_PREFILL_ROWS = 0
+
+
+class DecodeServer:
+    """Continuous batching over one TransformerLM: up to `rows` requests decode in one step (the captured decode step of
+    decode.LMDecodeSession), a queued request is admitted into a cache row as soon as one is free, and a finished row is
+    retired at once.  Every request's tokens are those of ``TransformerLM.inference`` run alone with its seed.
+
+    The server owns a private session over the model's shared packed weights (not one of ``decode_session``'s, which
+    ``inference_batch`` resets).  submit() / step() work on the current stream.  While requests are in flight the
+    weights must not change (RuntimeError; an idle server repacks), and an adapter must stay resident while a request
+    that uses it is alive."""
+
+    def __init__(self, lm: TransformerLM, rows: int, max_cache: int, prefill_rows: int, adapters: bool):
+        DEC.check_serve_rows(rows, prefill_rows)
+        self.lm, self.rows, self.prefill_rows, self.adapters = lm, int(rows), int(prefill_rows), bool(adapters)
+        self.cap = DEC.bucket(max_cache)
+        self.cfg = lm.sampler_cfg()
+        if self.cfg is None:
+            raise NotImplementedError("decode_server runs the device sampler only (see sampler_cfg)")
+        self.sched = DEC.RowScheduler(self.rows, self.prefill_rows)
+        self.req: Dict[int, dict] = {}                     # rid -> record; dropped by result() / cancel()
+        self.by_row: Dict[int, int] = {}                   # decoding rows -> rid
+        self.events: List[tuple] = []                      # finished without a step (max_len <= 0)
+        self.next_rid = 0
+        self.sess: Optional[DEC.LMDecodeSession] = None
+        self._pack()
+
+    # ---- weights
+    def _pack(self):
+        fold = not self.adapters
+        self.bank = None
+        stacks = None
+        if self.adapters:
+            from .adapters import bank_of
+            self.bank = bank_of(self.lm)
+        ver, pk = self.lm._decode_pack(fold)
+        if self.bank is not None:
+            stacks = self.bank.stacks(pk.wdtype)
+        self._params = [p for n, p in self.lm.named_parameters() if fold or 'lora_' not in n]
+        self._ver, self._dtype = ver, self.lm.numerics.dtype
+        self.sess = DEC.LMDecodeSession(pk, self.rows, self.cap, bank=stacks, prefill_rows=self.prefill_rows)
+        self.sess.idle(self.cfg)
+
+    def _check_weights(self):
+        if tuple(p._version for p in self._params) == self._ver and self.lm.numerics.dtype == self._dtype:
+            return
+        if self.pending():
+            raise RuntimeError("decode_server: the model's weights changed while requests are in flight")
+        self._pack()
+
+    # ---- requests
+    def pending(self) -> int:
+        """requests queued, being prefilled or decoding."""
+        return sum(1 for r in self.req.values() if r["state"] in ("queued", "running"))
+
+    @torch.no_grad()
+    def submit(self, text, *, embedding=None, prompt_text=None, prompt_speech_token=None, seed: Optional[int] = None,
+               adapter=None, min_token_text_ratio: float = 2, max_token_text_ratio: float = 20) -> int:
+        """Queue one request (``inference``'s operands: text without the prompt; embedding [1, 192] or None).  Its
+        lm_input rows are built now, with `adapter` activated for the text encoder.  -> the request id."""
+        self._check_weights()
+        if (adapter is not None) != self.adapters:
+            raise ValueError("decode_server: adapter= goes with decode_server(adapters=True), and every request of such a "
+                             "server names one (adapters.BASE for none)")
+        z = torch.zeros(0, dtype=torch.long)
+        text = torch.as_tensor(text, dtype=torch.long).reshape(-1)
+        pt = z if prompt_text is None else torch.as_tensor(prompt_text, dtype=torch.long).reshape(-1)
+        ps = z if prompt_speech_token is None else torch.as_tensor(prompt_speech_token, dtype=torch.long).reshape(-1)
+        emb = torch.zeros(1, 192) if embedding is None else embedding
+        emb = emb.reshape(1, -1) if emb.numel() else emb
+        n_text = text.numel()
+        min_len, max_len = int(n_text * min_token_text_ratio), int(n_text * max_token_text_ratio)
+        T = 2 + (1 if emb.shape[0] != 0 else 0) + pt.numel() + n_text + ps.numel()
+        if max_len > 0 and T + max_len > self.cap:           # on the host, before anything is launched
+            raise ValueError("decode capacity bucket too small")
+        slot = None
+        if self.adapters:
+            slot = self.bank.slot(adapter)
+        rid = self.next_rid
+        self.next_rid += 1
+        rec = self.req[rid] = dict(state="queued", tokens=[], row=None, first=False, error=False)
+        if max_len <= 0:
+            rec["state"] = "finished"
+            self.events.append((rid, None, True))
+            return rid
+        if self.adapters:
+            self.bank.activate(adapter)                       # the text encoder runs through its modules
+        x, _ = self.lm.lm_input_rows(text, n_text, pt, pt.numel(), ps, ps.numel(), emb)
+        assert x.shape[0] == T
+        rec.update(x=x, min_len=min_len, max_len=max_len, slot=slot,
+                   seed=self.lm._request_seed() if seed is None else int(seed))
+        self.sched.submit(rid, T)
+        return rid
+
+    @torch.no_grad()
+    def step(self, use_graph: bool = True) -> List[tuple]:
+        """Admit the oldest queued request if a row is free, run one step (the captured decode step, or one that also
+        carries prompt rows of the admission in flight), read the device once.  -> [(rid, token | None, finished), ...]
+        of this step: one entry per decoding request; EOS is not emitted (token None, finished True).  A request whose
+        row raised the sampler's error flag finishes alone with token None; result(rid) then raises."""
+        self._check_weights()
+        out, self.events = self.events, []
+        if not self.sched.busy():
+            return out
+        sess, eos = self.sess, self.lm.speech_token_size
+        p = self.sched.plan()
+        if p["admit"] is not None:
+            rid, row = p["admit"]
+            r = self.req[rid]
+            r["row"] = row
+            r["state"] = "running"
+            sess.admit(row, r.pop("x"), r["min_len"], r["max_len"], r["seed"], slot=r["slot"])
+        sess.serve_step(sum(p["chunks"]), use_graph)
+        if p["first"]:
+            self.by_row[p["row"]] = p["rid"]
+        if not self.by_row:
+            return out
+        tok, done, err = sess.read()
+        for row, rid in sorted(self.by_row.items()):
+            r = self.req[rid]
+            if err[row]:
+                r["error"] = True
+                out.append((rid, None, True))
+            elif tok[row] == eos:
+                out.append((rid, None, True))
+            else:
+                r["tokens"].append(tok[row])
+                out.append((rid, tok[row], bool(done[row])))
+            if out[-1][2]:
+                r["state"] = "finished"
+                self._free(rid)
+        return out
+
+    def _free(self, rid: int):
+        row = self.sched.release(rid)
+        if row is not None:
+            self.sess.retire(row)
+            self.by_row.pop(row, None)
+
+    def cancel(self, rid: int) -> None:
+        """drop a request at any stage: a queued one leaves the queue, a running one frees its row for the next."""
+        r = self.req.pop(rid)
+        if r["state"] in ("queued", "running"):
+            self._free(rid)
+
+    def result(self, rid: int) -> List[int]:
+        """the tokens of a finished request (its record is dropped); the reference's RuntimeError if its sampler kept
+        drawing EOS before min_len."""
+        r = self.req[rid]
+        if r["state"] != "finished":
+            raise RuntimeError(f"decode_server: request {rid} has not finished")
+        del self.req[rid]
+        if r["error"]:
+            raise RuntimeError(MAX_TRIALS_MSG.format(100))
+        return r["tokens"]
+
+    def run(self, use_graph: bool = True) -> Dict[int, List[int]]:
+        """step until nothing is pending; -> {rid: tokens} of every finished request that has not been collected (a
+        failed one is left for result(rid) to raise)."""
+        while self.pending():
+            self.step(use_graph)
+        self.events = []
+        out = {}
+        for rid in [k for k, r in self.req.items() if r["state"] == "finished" and not r["error"]]:
+            out[rid] = self.result(rid)
+        return out
 
 
 def build_llm_model(pretrained_path: Optional[str] = None, device: str = 'cuda', numerics: Optional[Numerics] = None,

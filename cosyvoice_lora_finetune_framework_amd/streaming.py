@@ -26,6 +26,8 @@ from .hipops import functional as HF
 
 SPEED_MSG = 'speed change only support non-stream inference mode'
 MEL_HOP, MEL_RATE = 256, 22050
+SERVE_KEYS = {"text_tokens", "prompt_wav", "prompt_rate", "prompt_speech_token", "prompt_text", "embedding", "prompt_feat",
+              "seed", "noise", "hift_seed", "hift_draws", "hift_dtype", "want_pcm", "adapter", "llm_kw"}
 
 
 class StreamState:
@@ -75,6 +77,7 @@ class StreamingSynthesizer:
         self.speech_window = np.hamming(2 * self.source_cache_len)
         self._dev_windows: Dict[torch.device, Tuple[torch.Tensor, torch.Tensor]] = {}
         self._llm_stream: Optional[torch.cuda.Stream] = None
+        self._servers: Dict[tuple, object] = {}          # serve(): (rows, prefill_rows, adapters, cache) -> DecodeServer
         self.last_timing: Dict[str, float] = {}
 
     # ------------------------------------------------------------------ host logic
@@ -313,3 +316,149 @@ class StreamingSynthesizer:
                 # whatever the LLM stream still runs (an abandoned request too) is ordered before the caller's next work:
                 # the decode session's buffers and the module caches are shared with non-streaming calls on that stream
                 caller.wait_stream(llm_stream)
+
+    # ------------------------------------------------------------------ many requests
+    @torch.no_grad()
+    def serve(self, requests, *, rows: int = 8, prefill_rows: Optional[int] = None, use_graph: bool = True,
+              max_cache: int = 2048) -> Iterator[Tuple[object, dict]]:
+        """Streamed synthesis of many requests at once: their LLM decodes share one ``DecodeServer`` (continuous batching,
+        `rows` requests per decode step, queued ones admitted as rows fall free) on the LLM stream, while each request's
+        chunks are cut by tts's own rule and run through token2wav on the caller's stream, one chunk at a time (the Flow and
+        the vocoder are not batched across requests).  Yields (key, item): tts's items plus 'final': bool, each request's
+        chunks in order and equal to ``tts(stream=True)`` of that request alone under the same seed / noise / hift pins.
+        A request whose LLM fails yields {'error': exception, 'final': True} and the others go on.
+
+        requests: an iterable of dicts with tts's keywords (text_tokens, prompt_wav, prompt_rate, prompt_speech_token,
+        prompt_text, embedding, prompt_feat, seed, noise, hift_seed, hift_draws, hift_dtype, want_pcm, adapter, llm_kw) and
+        an optional 'key' (default: its index).  It may be a generator: it is polled between decode steps, so requests
+        can arrive while others run; yielding None means "nothing now".  With an AdapterBank over the models every request
+        names its `adapter` (adapters.BASE for none).  max_cache: prompt rows + max_len a request's LLM decode may need."""
+        dev = self.flow.input_embedding.weight.device
+        caller = torch.cuda.current_stream(dev)
+        llm_stream = self.llm_stream(dev)
+        banked = "_cvft_adapter_bank" in self.llm.__dict__
+        skey = (rows, prefill_rows, banked, max_cache)
+        srv = self._servers.get(skey)
+        if srv is None:
+            self._servers.clear()                  # one server's caches at a time
+            srv = self._servers[skey] = self.llm.decode_server(rows=rows, max_cache=max_cache, prefill_rows=prefill_rows,
+                                                               adapters=banked)
+        it = iter(requests)
+        exhausted = False
+        live: Dict[int, dict] = {}                 # rid -> request state, in arrival order
+        index = 0
+        flight = None                              # the chunk on the caller's stream: (request, item, event)
+
+        def take(q: dict) -> None:
+            nonlocal index
+            q = dict(q)
+            key = q.pop("key", index)
+            index += 1
+            unknown = set(q) - SERVE_KEYS
+            if unknown:
+                raise ValueError(f"serve: unknown request fields {sorted(unknown)} (a request is streamed at speed 1 from text)")
+            adapter = q.get("adapter")
+            if q.get("text_tokens") is None:
+                raise ValueError("serve: every request needs text_tokens")
+            p_tok, p_text, emb, p_feat = self._prompt(dev, q.get("prompt_wav"), q.get("prompt_rate"),
+                                                      q.get("prompt_speech_token"), q.get("prompt_text"), q.get("embedding"))
+            if q.get("prompt_feat") is not None:
+                p_feat = q["prompt_feat"].float().to(dev)
+            # the request's lm_input rows are built on the caller's stream, in order with the chunks: both go through
+            # the modules an adapter is written into
+            rid = srv.submit(torch.as_tensor(q["text_tokens"], dtype=torch.long).reshape(-1).to(dev), embedding=emb,
+                             prompt_text=p_text, prompt_speech_token=p_tok, seed=q.get("seed"),
+                             **({} if adapter is None else {"adapter": adapter}), **(q.get("llm_kw") or {}))
+            x = srv.req[rid].get("x")
+            if x is not None:
+                x.record_stream(llm_stream)
+            llm_stream.wait_stream(caller)
+            live[rid] = dict(key=key, q=q, adapter=adapter, p_tok=p_tok, p_feat=p_feat, emb=emb, tokens=[], done=False,
+                             error=None, base=0, hop=self.token_min_hop_len, i=0, state=StreamState())
+
+        def poll() -> None:
+            nonlocal exhausted
+            while not exhausted and srv.pending() < 2 * rows:
+                try:
+                    q = next(it)
+                except StopIteration:
+                    exhausted = True
+                    return
+                if q is None:
+                    return
+                take(q)
+
+        def ready(r: dict) -> Optional[bool]:
+            """None: nothing to synthesise yet; else whether the next chunk is the final one."""
+            if len(r["tokens"]) - r["base"] >= r["hop"] + self.token_overlap_len:
+                return False
+            return True if r["done"] else None
+
+        def synthesise(r: dict, finalize: bool):
+            q, i = r["q"], r["i"]
+            noise, draws, hseed = q.get("noise"), q.get("hift_draws"), q.get("hift_seed")
+            window = r["tokens"][r["base"]:] if finalize else r["tokens"][r["base"]:r["base"] + r["hop"] + self.token_overlap_len]
+            if r["adapter"] is not None:
+                from .inference_joint import activate_adapter
+                activate_adapter(self.llm, self.flow, r["adapter"])
+            taps = {} if q.get("want_pcm") else None
+            wav = self.token2wav(r["state"], torch.tensor([window], dtype=torch.long), r["p_tok"], r["p_feat"], r["emb"],
+                                 finalize, noise=noise[i] if isinstance(noise, (list, tuple)) else noise,
+                                 hift_draws=draws[i] if isinstance(draws, list) else draws,
+                                 hift_seed=None if hseed is None else hseed + i, hift_dtype=q.get("hift_dtype"),
+                                 want_pcm=bool(q.get("want_pcm")), taps=taps)
+            item = {"tts_speech": wav, "final": finalize}
+            if taps is not None:
+                item["pcm"] = taps["pcm"]
+            ev = torch.cuda.Event()
+            ev.record(caller)
+            r["base"] += r["hop"]
+            r["hop"] = min(self.token_max_hop_len, int(r["hop"] * self.stream_scale_factor))
+            r["i"] += 1
+            return item, ev
+
+        try:
+            llm_stream.wait_stream(caller)
+            while True:
+                poll()
+                if srv.pending() or srv.events:
+                    with torch.cuda.stream(llm_stream):
+                        events = srv.step(use_graph)
+                    for rid, tok, fin in events:
+                        r = live[rid]
+                        if tok is not None:
+                            r["tokens"].append(tok)
+                        if fin:
+                            r["done"] = True
+                            try:
+                                srv.result(rid)
+                            except RuntimeError as e:
+                                r["error"] = e
+                            if not r["tokens"] and r["error"] is None:
+                                r["error"] = RuntimeError("the LLM produced no speech tokens")
+                if flight is not None and (flight[2].query() or not srv.pending()):
+                    r, item, ev = flight
+                    ev.synchronize()
+                    flight = None
+                    yield r["key"], item
+                if flight is None:
+                    for rid, r in list(live.items()):
+                        if r["error"] is not None:
+                            del live[rid]
+                            yield r["key"], {"error": r["error"], "final": True}
+                            continue
+                        fin = ready(r)
+                        if fin is None:
+                            continue
+                        item, ev = synthesise(r, fin)
+                        flight = (r, item, ev)
+                        if fin:
+                            del live[rid]
+                        break
+                if flight is None and not live and exhausted and not srv.pending():
+                    return
+        finally:
+            for rid, r in live.items():
+                if not r["done"]:
+                    srv.cancel(rid)
+            caller.wait_stream(llm_stream)

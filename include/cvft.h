@@ -566,6 +566,13 @@ int cvft_debug_mfma_fp8_probe(const void* A, const void* B, float* C, void* stre
  *   P [>= cap][ldp]: P[d] = linear_pos(pe at relative distance d >= 0).  done[b] != 0 (or done NULL = none): row skipped,
  *   nothing written to its cache, o rows zero.  Keys are split over `nsplit` workgroups of 256 keys (nsplit*256 >= cap);
  *   part = workspace of B*H*nsplit*Lq*66 floats, combined by a second launch.
+ * cvft_decode_attn_ragged: cvft_decode_attn driven by a segment table instead of a uniform (B, Lq): seg [nseg][3] (device
+ *   int32) = (cache row b, first activation row q0, Lq); segment s attends rows q0 .. q0+Lq-1 of qkv / o [M][..] against
+ *   cache row b of kc / vc [nrows][H][cap][64] from len[b] and appends their K/V there.  nseg <= 16, M <= 16 activation
+ *   rows in all, each Lq >= 1, segments disjoint in rows and in cache rows (the caller lists live sequences only: there
+ *   is no done input; cache rows no segment names are neither read nor written).  A segment outside these bounds is
+ *   skipped whole.  part = workspace of M*H*nsplit*66 floats.  Per query row the arithmetic and its order are
+ *   cvft_decode_attn's (both launch the same device functions), so a row equals that sequence run alone bit for bit.
  * cvft_decode_sample: one workgroup per row b (not done): logp = log_softmax(logits[b]) (written to logp if non-NULL);
  *   step 0 -> logp[eos] = -inf; probabilities = softmax(logp); mode 0 RAS (common.py:111-139: nucleus over the stable
  *   descending order while cum < top_p and count < top_k, top_k <= 64; the drawn id redrawn from the full softmax when it
@@ -597,6 +604,10 @@ int cvft_decode_linear_lora(int wdtype, int M, int N, int K, const float* X, int
 int cvft_decode_attn(int B, int H, int Lq, int cap, int nsplit, const float* qkv, int ldqkv, float* kc, float* vc,
                      const int32_t* len, const int32_t* done, const float* P, int ldp, const float* pos_bias_u,
                      const float* pos_bias_v, float scale, float* part, float* o, int ldo, void* stream);
+int cvft_decode_attn_ragged(int nseg, int M, int nrows, int H, int cap, int nsplit, const int32_t* seg, const float* qkv,
+                            int ldqkv, float* kc, float* vc, const int32_t* len, const float* P, int ldp,
+                            const float* pos_bias_u, const float* pos_bias_v, float scale, float* part, float* o, int ldo,
+                            void* stream);
 int cvft_decode_sample(int B, int V, const float* logits, int ldl, float* logp, int eos, int mode, int top_k,
                        float top_p, int win, int rep_thr, const uint64_t* seeds, const float* uniforms, int32_t* tok,
                        int32_t* next_in, int32_t* hist, int hist_cap, int32_t* nhist, int32_t* step,
